@@ -19,6 +19,20 @@ skipped) bracketed by barrier + synchronize; the slowest rank's time counts.  We
 per-GPU batch is fixed, so the aggregate tokens/s is reported for the whole job, plus per-rank
 tokens/s and the exposed all-reduce time (communication not hidden behind the backward).
 
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the
+result line.  ``--full`` is where every further measurement of this benchmark goes (a CPU baseline,
+another precision or size, a comparison, a per-kernel table: anything that takes runs of its own);
+today there is none, so the flag changes nothing but the ``full`` field of the result line.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed ``train_step`` computed
+as float32 ``DIR/<name>.npy`` (rank 0's replica): ``loss`` (the step's mean loss), ``grad_norm`` (the
+global gradient norm it clipped by), and ``grads`` / ``params`` — the gradients it reduced and the
+parameters it wrote, flattened in ``named_parameters`` order and, above ``DUMP_SAMPLE`` elements,
+cut down to one fixed seeded sample of positions (``sample_index`` holds them).  The fused path
+keeps the gradients unclipped (the clip factor goes into AdamW); ``--path module`` leaves them as
+``clip_grad_norm_`` scaled them.  Model init, data
+and sample are seeded, so two builds run with the same arguments can be compared output for output.
+
 ``--device cpu`` (gloo, fp32, ``--model tiny``) exists for the CPU contract tests only.
 """
 
@@ -32,6 +46,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -87,6 +102,45 @@ def summarize_buckets(steps: list[list[dict[str, float]]]) -> list[dict[str, flo
                 summary[key] = round(sum(vals) / len(vals), 3)
         out.append(summary)
     return out
+
+
+DUMP_SAMPLE = 1 << 21  # elements kept of grads / params (8 MiB each as float32; 32 MiB with the index)
+DUMP_SEED = 20240607
+
+
+def sample_positions(total: int) -> np.ndarray:
+    """The sorted positions of the flattened parameters that ``--dump-outputs`` keeps: all of them
+    up to ``DUMP_SAMPLE``, else a sample without replacement fixed by ``DUMP_SEED`` and ``total``."""
+    if total <= DUMP_SAMPLE:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=DUMP_SAMPLE, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir: str, model: torch.nn.Module, loss: torch.Tensor, grad_norm: torch.Tensor | None) -> None:
+    """Write what the last timed step computed (see the module docstring) as ``out_dir/<name>.npy``."""
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    missing = [n for n, p in model.named_parameters() if p.grad is None]
+    if missing or grad_norm is None:
+        raise RuntimeError(f"--dump-outputs: the last step left no gradient norm or no gradient for {missing[:4]}")
+    pos = sample_positions(sum(p.numel() for p in params))
+    grads, values, offset = [], [], 0
+    for p in params:
+        lo, hi = np.searchsorted(pos, [offset, offset + p.numel()])
+        if hi > lo:
+            idx = torch.from_numpy(pos[lo:hi] - offset).to(p.device)
+            values.append(p.detach().reshape(-1).index_select(0, idx).float().cpu())
+            grads.append(p.grad.detach().reshape(-1).index_select(0, idx).float().cpu())
+        offset += p.numel()
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu().numpy(),
+        "grad_norm": grad_norm.detach().float().reshape(1).cpu().numpy(),
+        "grads": torch.cat(grads).numpy(),
+        "params": torch.cat(values).numpy(),
+        "sample_index": pos.astype(np.float64),  # exact: positions stay far below 2**53
+    }
+    for name, array in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), array)
 
 
 def make_config(args: argparse.Namespace, world: int):
@@ -160,6 +214,10 @@ def main() -> int:
                     help="fused engine: what the MLP keeps for its backward (model.extra.mlp_store)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo on GPU: rehearse the N-rank path on a box with fewer GPUs (ranks share devices)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure (none today; see the docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -221,6 +279,8 @@ def main() -> int:
     want = args.steps * cfg.trainer.micro_batch_size * cfg.trainer.grad_accum_steps * cfg.model.block_size
     if tokens != want:  # a short data shard would silently shrink the per-GPU batch
         raise RuntimeError(f"rank {rank}: timed {tokens} tokens, expected {want}")
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, getattr(trainer.model, "module", trainer.model), loss, trainer.last_grad_norm)
 
     mine = torch.tensor([elapsed, float(tokens), comm_ms], dtype=torch.float64, device=dev)
     if world > 1:
@@ -248,6 +308,7 @@ def main() -> int:
             "ms_per_step": round(1000.0 * elapsed / args.steps, 3),
             "higher_is_better": True,
             "scaling": "weak",
+            "full": bool(args.full),
             "vs_baseline": None,
             "dtype": "bf16" if gpu else "fp32",
             "data": "synthetic (seeded Markov token windows, full block_size), random-init weights",

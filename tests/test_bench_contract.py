@@ -12,6 +12,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 from llmtrain.data.synthetic_tokens import SyntheticTokensDataModule
@@ -92,6 +93,47 @@ def test_bench_rejects_world_size_mismatch() -> None:
     proc = _run_bench("--gpus", "2", env_extra={"WORLD_SIZE": "1"})
     assert proc.returncode == 2
     assert "WORLD_SIZE=1" in proc.stderr
+
+
+def test_dump_sample_is_fixed_sorted_and_bounded() -> None:
+    bench = _bench()
+    small = bench.sample_positions(1000)
+    assert small.tolist() == list(range(1000))  # below the cap: every position
+    total = 3 * bench.DUMP_SAMPLE + 7
+    pos = bench.sample_positions(total)
+    assert pos.shape == (bench.DUMP_SAMPLE,) and pos.dtype == np.int64
+    assert (np.diff(pos) > 0).all() and pos[0] >= 0 and pos[-1] < total  # sorted, distinct, in range
+    assert np.array_equal(pos, bench.sample_positions(total))  # the same sample every time
+    # loss + grad_norm + grads + params (float32) + sample_index (float64) stay far below 64 MB
+    assert 2 * 4 + bench.DUMP_SAMPLE * (4 + 4 + 8) <= 32 * 2**20 + 8
+
+
+def test_bench_dump_outputs_and_full(tmp_path: Path) -> None:
+    """``--dump-outputs`` writes what the last timed step computed, the same from run to run with
+    the same arguments (seeded init, data and sample); ``--full`` is accepted, exits 0 and leaves
+    the headline fields of the result line as they are."""
+    runs = []
+    for name, extra in (("a", ()), ("b", ("--full",))):
+        proc = _run_bench("--gpus", "1", "--dump-outputs", str(tmp_path / name), *extra)
+        assert proc.returncode == 0, proc.stderr[-3000:]
+        res = _json_line(proc.stdout)
+        assert res["full"] is bool(extra) and res["steps"] == 2 and res["ms_per_step"] > 0
+        arrays = {p.stem: np.load(p) for p in sorted((tmp_path / name).glob("*.npy"))}
+        assert set(arrays) == {"loss", "grad_norm", "grads", "params", "sample_index"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 10**6
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        assert arrays["grads"].shape == arrays["params"].shape == arrays["sample_index"].shape
+        assert arrays["grads"].size > 0 and np.abs(arrays["grads"]).max() > 0
+        assert abs(float(arrays["loss"][0]) - res["final_loss"]) <= 1e-4  # the last timed step's loss
+        # the norm of the dumped gradients (tiny model: every element is kept) is the dumped norm
+        assert np.linalg.norm(arrays["grads"].astype(np.float64)) == pytest.approx(float(arrays["grad_norm"][0]), rel=1e-4)
+        runs.append((res, arrays))
+    (res_a, a), (res_b, b) = runs
+    for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "config"):
+        assert res_a[key] == res_b[key]
+    for name in a:  # fp32 on CPU with a fixed thread count: the same sums in the same order
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-6, atol=1e-8, err_msg=name)
 
 
 def test_bench_single_rank_cpu_contract() -> None:
