@@ -25,7 +25,7 @@ def main() -> None:
     if arm == "library":
         from llmtrain import ops
 
-        ops.head_logits = lambda h, w: ops._lib_mm(h, w.t(), op="LM-head logits")  # rounds 1-5 routing
+        ops.head_logits = lambda h, w: ops.gemm._lib_mm(h, w.t(), op="LM-head logits")  # rounds 1-5 routing
     sys.argv = [os.path.join(ROOT, "bench.py"), *sys.argv[2:]]
     runpy.run_path(sys.argv[0], run_name="__main__")
 

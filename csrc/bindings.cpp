@@ -554,7 +554,7 @@ std::tuple<Tensor, c10::optional<Tensor>> gemm_fused(const Tensor& a, const Tens
   const bool gelu_out = epilogue == 1 || epilogue == 4;
   // the kernel's buffer descriptors and tile offsets are 32-bit byte offsets: every operand and
   // output (a [M,K], b, out / u / c2 [M,N]) must stay below 2 GiB, else loads read zeros and
-  // stores drop silently — callers split larger GEMMs into row chunks (llmtrain/ops, _gemm_rows)
+  // stores drop silently — callers split larger GEMMs into row chunks (llmtrain/ops/gemm.py, row_chunks)
   TORCH_CHECK(M * std::max(K, N) * 2 < (int64_t(1) << 31) && K * N * 2 < (int64_t(1) << 31),
               "gemm_fused: an operand or output reaches 2 GiB (M=", M, ", K=", K, ", N=", N,
               "); split the rows");

@@ -8,12 +8,13 @@
 //   1  U = bf16(acc + bias), C2 = bf16(gelu(U))  (fc forward: pre-activation kept for backward)
 //   2  C = bf16(acc * gelu'(U)), dbias += colsum(C)   (proj dX: GELU backward + fc bias grad)
 //   3  C = bf16(acc), delta[b, h, t] = sum_d C[m, 64h + d] * U[m, 64h + d], dbias += colsum(C)
-//   4  u = bf16(acc + bias), C = bf16(gelu'(u)), C2 = bf16(gelu(u))  (fc forward keeping the GELU
-//      derivative instead of the pre-activation: the backward's epilogue 5 then skips the erf math)
-//   5  C = bf16(acc * U), dbias += colsum(C)  (U = the stored gelu'(u): proj dX + GELU backward)
 //      (attention out-proj dX = dO; U = the attention output O: the flash-attention backward's
 //      row constant and, without dropout, the V part of the qkv bias gradient — each wave's 64
 //      output columns are exactly one head, so the per-head dot product never leaves the wave)
+//   4  u = bf16(acc + bias), C = bf16(gelu'(u)), C2 = bf16(gelu(u))  (fc forward keeping the GELU
+//      derivative instead of the pre-activation: the backward's epilogue 5 then skips the erf math)
+//   5  C = bf16(acc * U), dbias += colsum(C)  (U = the stored gelu'(u): proj dX + GELU backward)
+// (llmtrain/ops/gemm.py names these values: Epilogue)
 //
 // Why: in the GPT MLP (reference models/gpt.py:94-105, nn.Linear -> nn.GELU -> nn.Linear) the
 // library GEMM writes the pre-activation, a separate pass reads it and writes gelu(u), and in the

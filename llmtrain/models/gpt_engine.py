@@ -3,16 +3,20 @@
 The engine runs a whole forward + loss, and later the whole backward, as one explicitly
 scheduled sequence of kernels instead of an autograd graph of small ops:
 
-forward (per block; ``M = B*T`` tokens, ``d`` model width, residual stream kept in fp32)::
+forward (per block; ``M = B*T`` tokens, ``d`` model width; the residual stream is stored in bf16
+with the bf16 compute dtype, in fp32 otherwise: ``residual`` below)::
 
     x_s, h1  = add_layernorm(x, delta)            # HIP: residual add fused into LN, bf16 out
-    qkv      = h1 @ Wqkv^T + b                    # hipBLASLt (bias epilogue), bf16
+    qkv      = h1 @ Wqkv^T + b                    # GEMM, bias in its epilogue, bf16
     att, lse = flash_attn_fwd(qkv)                # HIP: gfx950 MFMA, packed qkv, causal
-    y        = att @ Wo^T + b                     # hipBLASLt
+    y        = att @ Wo^T + b                     # GEMM
     x_m, h2  = add_layernorm(x_s, y)              # HIP
-    u        = h2 @ Wfc^T + b                     # hipBLASLt
-    g        = gelu(u)                            # HIP (exact erf GELU)
-    delta    = g @ Wproj^T + b                    # hipBLASLt  (added by the next LN)
+    u | gd   = h2 @ Wfc^T + b                     # GEMM with the exact-erf GELU in its epilogue:
+    g        = gelu(u)                            #   keeps u, or gelu'(u) (``mlp_store``)
+    delta    = g @ Wproj^T + b                    # GEMM  (added by the next LN)
+
+Each forward / dX GEMM runs on the hand-written fused-epilogue kernel (csrc/gemm_fused.hip) or on
+hipBLASLt (then with separate GELU passes), as :mod:`llmtrain.ops.gemm` routes its shape.
 
 Dropout (reference ``nn.Dropout`` after the embeddings, on the attention probabilities and on
 both residual branches, active in train mode) is fused into those kernels: each site's keep-mask
@@ -58,10 +62,6 @@ __all__ = ["FusedGPTEngine"]
 VOCAB_PAD = 64  # pad the LM-head rows to a multiple of the MFMA-friendly tile
 
 
-def _mm(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    return torch.mm(a, b)
-
-
 _WGRAD_MODE: dict[str, str] = {}
 
 
@@ -93,18 +93,18 @@ def accumulate_wgrad(dst: torch.Tensor, dy: torch.Tensor, x: torch.Tensor) -> No
 
 @dataclass
 class _BlockActs:
-    xs: torch.Tensor  # fp32 residual stream entering the attention sub-block
+    xs: torch.Tensor  # residual stream (engine.res_dtype) entering the attention sub-block
     h1: torch.Tensor
     mu1: torch.Tensor
     rs1: torch.Tensor
     qkv: torch.Tensor
     att: torch.Tensor
     lse: torch.Tensor
-    xm: torch.Tensor  # fp32 residual stream entering the MLP sub-block
+    xm: torch.Tensor  # residual stream entering the MLP sub-block
     h2: torch.Tensor
     mu2: torch.Tensor
     rs2: torch.Tensor
-    u: torch.Tensor
+    u: torch.Tensor  # fc pre-activation, or gelu'(u) with mlp_store "gd"
     g: torch.Tensor
 
 
@@ -236,10 +236,10 @@ class FusedGPTEngine:
             # measured (docs/round6.md §8): "gd" +0.5 % at GPT-2 124M (d 768: the fc forward's fused
             # epilogue costs less than the erf it saves the dX), -0.7 % at GPT-2 XL (d 1600: the
             # library's fc forward + GELU pass stays ahead of the fused fc forward)
-            mlp_store = "gd" if self.fused_gemm and model.d_model <= MLP_STORE_GD_MAX_D else "u"
+            mlp_store = "gd" if model.d_model <= MLP_STORE_GD_MAX_D else "u"
         if mlp_store not in ("u", "gd"):
             raise ValueError(f"mlp_store must be 'u' or 'gd', not {mlp_store!r}")
-        self.mlp_store = mlp_store
+        self.mlp_store = mlp_store if self.fused_gemm else "u"  # "gd" exists for the fused epilogue
         self.markers = os.environ.get("LLMTRAIN_ROCTX", "0") == "1" and self.store.device.type == "cuda"
         # set by a Trainer with run.deterministic: warn once if a step runs outside its kernel policy
         self.expect_deterministic = False
@@ -315,16 +315,17 @@ class FusedGPTEngine:
         self._held.clear()
         self._pending = []
 
-    def _linear(self, x: torch.Tensor, layer: torch.nn.Linear, *, fused: bool = False) -> torch.Tensor:
-        w = self._w(layer.weight)
-        b = None if layer.bias is None else self._w(layer.bias)
-        if fused and self.fused_gemm:
-            return ops.linear_fwd(x, w, b)
-        return torch.mm(x, w.t()) if b is None else torch.addmm(b, x, w.t())
+    def _gemm(self, op: Callable[..., Any], *args: Any, **kw: Any) -> Any:
+        """A block's forward / dX GEMM ``op`` (an ``ops.linear_*`` function, routed by
+        :mod:`llmtrain.ops.gemm`); LLMTRAIN_FUSED_GEMM=0 keeps it on the library."""
+        return op(*args, allow_ours=self.fused_gemm, **kw)
+
+    def _linear(self, x: torch.Tensor, layer: torch.nn.Linear) -> torch.Tensor:
+        return self._gemm(ops.linear_fwd, x, self._w(layer.weight), None if layer.bias is None else self._w(layer.bias))
 
     def loss(self, ids: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor | None) -> torch.Tensor:
         if not self.fused_gemm and self.store.device.type == "cuda":
-            ops._det_fallback("every GEMM (LLMTRAIN_FUSED_GEMM=0)")
+            ops.gemm._det_fallback("every GEMM (LLMTRAIN_FUSED_GEMM=0)")
         if self.expect_deterministic and not self._warned_policy and self.store.device.type == "cuda" \
                 and not ops.policy_state()[0]["deterministic"]:
             # a Trainer configured run.deterministic scopes its own steps (Trainer.kernel_policy);
@@ -390,24 +391,20 @@ class FusedGPTEngine:
             xs, h1, mu1, rs1 = ops.add_layernorm_fwd(
                 x, delta, blk.ln_1.weight, blk.ln_1.bias, self.eps, cdt, dropout=state.site(3 * i)
             )  # site 3i = the previous block's MLP branch (unused for block 0: delta is None)
-            qkv = self._linear(h1, blk.attn.qkv_proj, fused=True)
+            qkv = self._linear(h1, blk.attn.qkv_proj)
             att, lse = ops.attn_fwd(
                 qkv, bsz, seqlen, self.n_heads, dropout=state.site(2 + 3 * i), key_masks=state.key_masks
             )
-            y = self._linear(att, blk.attn.out_proj, fused=True)
+            y = self._linear(att, blk.attn.out_proj)
             if state.keep_col is not None:  # padded query rows add nothing to the residual stream
                 y = y * state.keep_col
             xm, h2, mu2, rs2 = ops.add_layernorm_fwd(
                 xs, y, blk.ln_2.weight, blk.ln_2.bias, self.eps, cdt, dropout=state.site(1 + 3 * i)
             )
-            if self.fused_gemm and self.mlp_store == "gd":  # keeps gelu'(u) for the backward (in "u")
-                u, g = ops.linear_fwd_gelu_gd(h2, self._w(blk.mlp_fc.weight), self._w(blk.mlp_fc.bias))
-            elif self.fused_gemm:  # bias + exact-erf GELU in the fc GEMM's epilogue
-                u, g = ops.linear_fwd_gelu(h2, self._w(blk.mlp_fc.weight), self._w(blk.mlp_fc.bias))
-            else:
-                u = self._linear(h2, blk.mlp_fc)
-                g = ops.gelu_fwd(u)
-            delta = self._linear(g, blk.mlp_proj, fused=True)
+            # bias + exact-erf GELU in the fc GEMM's epilogue; "gd" keeps gelu'(u) for the backward (in "u")
+            fc = ops.linear_fwd_gelu_gd if self.mlp_store == "gd" else ops.linear_fwd_gelu
+            u, g = self._gemm(fc, h2, self._w(blk.mlp_fc.weight), self._w(blk.mlp_fc.bias))
+            delta = self._linear(g, blk.mlp_proj)
             x = xm
             if keep:
                 state.blocks.append(_BlockActs(xs, h1, mu1, rs1, qkv, att, lse, xm, h2, mu2, rs2, u, g))
@@ -487,17 +484,11 @@ class FusedGPTEngine:
             # MLP: delta = g Wp^T + bp ; dx is d(delta).  Every bias gradient of the block is the
             # column sum of the output gradient its weight-gradient GEMM streams: summed there
             self._wgrad(self._g(blk.mlp_proj.weight), dx_lp, a.g, self._g(blk.mlp_proj.bias))
-            if self.fused_gemm and self.mlp_store == "gd":  # a.u holds gelu'(u): one multiply
-                du = ops.linear_dx_gd(dx_lp, self._w(blk.mlp_proj.weight), a.u)
-            elif self.fused_gemm:  # GELU backward in the dX GEMM's epilogue
-                du = ops.linear_dx_gelu_bwd(dx_lp, self._w(blk.mlp_proj.weight), a.u)
-            else:
-                dg = torch.mm(dx_lp, self._w(blk.mlp_proj.weight))
-                du = ops.gelu_bwd(dg, a.u, None)
-                del dg
+            # GELU backward in the dX GEMM's epilogue; with "gd" a.u holds gelu'(u): one multiply
+            proj_dx = ops.linear_dx_gd if self.mlp_store == "gd" else ops.linear_dx_gelu_bwd
+            du = self._gemm(proj_dx, dx_lp, self._w(blk.mlp_proj.weight), a.u)
             self._wgrad(self._g(blk.mlp_fc.weight), du, a.h2, self._g(blk.mlp_fc.bias))
-            wf = self._w(blk.mlp_fc.weight)
-            dh2 = ops.linear_dx(du, wf) if self.fused_gemm else torch.mm(du, wf)
+            dh2 = self._gemm(ops.linear_dx, du, self._w(blk.mlp_fc.weight))
             del du
             # ln_2's dgamma / dbeta partial rows wait for ln_1's: one reduce launch per block
             dxm, dy_lp, ln2_parts = ops.layernorm_bwd(
@@ -509,24 +500,18 @@ class FusedGPTEngine:
                 dy_lp = dy_lp * st.keep_col
             # attention output projection
             self._wgrad(self._g(blk.attn.out_proj.weight), dy_lp, a.att, self._g(blk.attn.out_proj.bias))
+            # dO plus the attention backward's row constants from one GEMM epilogue
+            # (not taken -> delta None: attn_bwd computes them itself)
             wo = self._w(blk.attn.out_proj.weight)
-            attn_drop = st.site(2 + 3 * i)
-            delta = None
-            if self.fused_gemm:
-                # dO plus the attention backward's row constants from one GEMM epilogue
-                # (not taken -> delta None: attn_bwd computes them itself)
-                datt, delta = ops.linear_dx_attn(dy_lp, wo, a.att, seqlen, head_dim=self.head_dim)
-            else:
-                datt = torch.mm(dy_lp, wo)
+            datt, delta = self._gemm(ops.linear_dx_attn, dy_lp, wo, a.att, seqlen, head_dim=self.head_dim)
             del dy_lp
             dqkv = ops.attn_bwd(
-                datt, a.qkv, a.att, a.lse, bsz, seqlen, self.n_heads, dropout=attn_drop, delta=delta,
+                datt, a.qkv, a.att, a.lse, bsz, seqlen, self.n_heads, dropout=st.site(2 + 3 * i), delta=delta,
                 key_masks=st.key_masks,
             )
             del datt
             self._wgrad(self._g(blk.attn.qkv_proj.weight), dqkv, a.h1, self._g(blk.attn.qkv_proj.bias))
-            wq = self._w(blk.attn.qkv_proj.weight)
-            dh1 = ops.linear_dx(dqkv, wq) if self.fused_gemm else torch.mm(dqkv, wq)
+            dh1 = self._gemm(ops.linear_dx, dqkv, self._w(blk.attn.qkv_proj.weight))
             del dqkv
             dx, dx_lp, ln1_parts = ops.layernorm_bwd(
                 dh1, a.xs, a.mu1, a.rs1, blk.ln_1.weight, dxm, self._g(blk.ln_1.weight), self._g(blk.ln_1.bias),

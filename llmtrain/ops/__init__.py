@@ -4,135 +4,34 @@ Each function runs the hand-written gfx950 HIP kernel (``torch.ops.llmtrain_hip.
 inputs live on a GPU and the plain-PyTorch oracle from :mod:`llmtrain.ops.reference` when they
 live on the CPU (unit tests of the fused engine).  There is exactly one GPU implementation per
 op and no silent fallback: a GPU tensor with the extension missing raises (``_ext.require``).
+The forward / data-gradient GEMMs and their routing live in :mod:`llmtrain.ops.gemm`, the
+process-wide kernel policy in :mod:`llmtrain.ops.policy`; both are re-exported here, and callers
+(the engine, the A/B scripts under bench/) reach every op through this package.
 """
 
 from __future__ import annotations
 
-import contextlib
-import os
-from collections.abc import Iterator
-
 import torch
 
-from llmtrain.ops import _ext
 from llmtrain.ops import reference as ref
+from llmtrain.ops._ext import hip_ops
+from llmtrain.ops.gemm import head_dx, head_logits, linear_dx, linear_dx_gd, linear_dx_gelu_bwd, linear_fwd
+from llmtrain.ops.gemm import linear_fwd_gelu, linear_fwd_gelu_gd, wgrad_accum
+from llmtrain.ops.gemm import linear_dx_attn  # noqa: F401 - public, though __all__ never listed it
+from llmtrain.ops.policy import _POLICY  # noqa: F401 - the flags themselves, for tests that read them
+from llmtrain.ops.policy import kernel_policy, policy_state, restore_policy, set_deterministic, single_stream
 
 __all__ = [
-    "adamw_flat",
-    "add_layernorm_fwd",
-    "attn_bwd",
-    "attn_fwd",
-    "attn_key_masks",
-    "clip_coef",
-    "colsum_accum",
-    "cross_entropy_fwd_bwd",
-    "embedding_bwd",
-    "embedding_fwd",
-    "gelu_bwd",
-    "gelu_fwd",
-    "head_dx",
-    "head_logits",
-    "hip_ops",
-    "kernel_policy",
-    "layernorm_bwd",
-    "linear_dx",
-    "linear_dx_gd",
-    "linear_dx_gelu_bwd",
-    "linear_fwd",
-    "linear_fwd_gelu",
-    "linear_fwd_gelu_gd",
-    "ln_param_reduce",
-    "policy_state",
-    "restore_policy",
-    "scale",
-    "set_deterministic",
-    "single_stream",
-    "sumsq",
-    "wgrad_accum",
+    "adamw_flat", "add_layernorm_fwd", "attn_bwd", "attn_fwd", "attn_key_masks", "clip_coef", "colsum_accum",
+    "cross_entropy_fwd_bwd", "embedding_bwd", "embedding_fwd", "gelu_bwd", "gelu_fwd", "head_dx", "head_logits", "hip_ops",
+    "kernel_policy", "layernorm_bwd", "linear_dx", "linear_dx_gd", "linear_dx_gelu_bwd", "linear_fwd", "linear_fwd_gelu",
+    "linear_fwd_gelu_gd", "ln_param_reduce", "policy_state", "restore_policy", "scale", "set_deterministic", "single_stream",
+    "sumsq", "wgrad_accum",
 ]
-
-
-def hip_ops():  # noqa: ANN201 - torch op namespace
-    _ext.require()
-    return torch.ops.llmtrain_hip
 
 
 def _on_gpu(t: torch.Tensor) -> bool:
     return t.device.type == "cuda"
-
-
-_POLICY = {"gemm_all_ours": False, "single_stream": False, "deterministic": False}
-
-# How run.deterministic keeps the step bitwise reproducible (LLMTRAIN_DET_SCHEDULE overrides):
-#  * "serial": the weight-gradient GEMMs run on the main stream (no side stream), the LM-head logits
-#    and dX GEMMs on our fixed-order kernel (the logits' tuned library solution is a Stream-K kernel
-#    and the one library GEMM of the configuration whose bitwise guarantee failed once,
-#    profiles/r5/det/; round 6 took it off the library), and the other forward / dX GEMMs on our
-#    kernel below the size cap, on hipBLASLt's tuned solutions above it.  Evidence for the library
-#    GEMMs that remain: bitwise-equal repeats at micro-batch 32 of GPT-2 124M and GPT-2 XL (the
-#    XL preset; 3 whole runs x 20 steps) (bench/determinism_probe.py, profiles/r4/det/,
-#    profiles/r5/det/) and 800 bitwise repeats of the Stream-K solutions of the forward
-#    projections, alone and beside a concurrent stream (bench/sk_repeat.py); other shapes are
-#    unpinned, and each library GEMM of a serial run is named once in the log (_det_library).
-#  * "ours": every forward / dX GEMM on the hand-written kernel (csrc/gemm_fused.hip), side stream
-#    kept; slower because that kernel trails hipBLASLt at 128K rows (docs/round4.md).
-DET_SCHEDULES = ("serial", "ours")
-
-
-def set_deterministic(on: bool, schedule: str | None = None) -> bool:
-    """Process-wide deterministic mode of the HIP kernels (``run.deterministic`` on GPU): the
-    split-K weight-gradient GEMM and the embedding token gradient switch from float atomics to
-    fixed-order reductions (every other reduction is fixed-order always), and the GEMM schedule
-    becomes one of :data:`DET_SCHEDULES` — hipBLASLt's Stream-K solutions combine partial tiles in
-    an order that depends on which workgroups finish first, which the weight-gradient side stream
-    perturbs (bench/determinism_probe.py --runs, docs/round3.md).  Returns the previous setting.
-    The CPU reference ops are deterministic anyway.  Prefer :func:`kernel_policy`, which restores
-    the previous policy on exit (the Trainer scopes its steps with it)."""
-    if on:
-        schedule = schedule or os.environ.get("LLMTRAIN_DET_SCHEDULE", "serial")
-        if schedule not in DET_SCHEDULES:
-            raise ValueError(f"deterministic schedule must be one of {DET_SCHEDULES}, not {schedule!r}")
-    _POLICY["gemm_all_ours"] = bool(on) and schedule == "ours"
-    _POLICY["single_stream"] = bool(on) and schedule == "serial"
-    _POLICY["deterministic"] = bool(on)
-    if not _ext.load():
-        return False
-    prev = bool(torch.ops.llmtrain_hip.get_deterministic())
-    torch.ops.llmtrain_hip.set_deterministic(bool(on))
-    return prev
-
-
-def policy_state() -> tuple[dict[str, bool], bool]:
-    """Snapshot of the process-wide kernel policy: the Python routing flags and the C++
-    deterministic flag (False when the extension is not loaded)."""
-    cpp = bool(torch.ops.llmtrain_hip.get_deterministic()) if _ext.is_loaded() else False
-    return dict(_POLICY), cpp
-
-
-def restore_policy(state: tuple[dict[str, bool], bool]) -> None:
-    """Undo every policy change since :func:`policy_state` returned ``state``."""
-    flags, cpp = state
-    _POLICY.update(flags)
-    if _ext.is_loaded():
-        torch.ops.llmtrain_hip.set_deterministic(bool(cpp))
-
-
-@contextlib.contextmanager
-def kernel_policy(deterministic: bool, schedule: str | None = None) -> Iterator[None]:
-    """Run a block under ``run.deterministic = deterministic`` and restore the previous policy on
-    exit, so one Trainer's setting never leaks into the next one in the same process (a test
-    suite, a notebook)."""
-    prev = policy_state()
-    set_deterministic(deterministic, schedule)
-    try:
-        yield
-    finally:
-        restore_policy(prev)
-
-
-def single_stream() -> bool:
-    """True when the deterministic "serial" schedule forbids the weight-gradient side stream."""
-    return _POLICY["single_stream"]
 
 
 def add_layernorm_fwd(x, delta, weight, bias, eps: float, out_dtype: torch.dtype, dropout=(0.0, 0)):
@@ -298,297 +197,6 @@ def attn_bwd(
     if qkv_bias_grad is not None:
         ref.colsum_accum(dqkv, qkv_bias_grad)
     return dqkv
-
-
-# Where the fused GEMM pays in a real step (same-box A/B, docs/performance.md): GPT-2 XL micro-batch
-# 16 (A operands 52 MB) +3 %; GPT-2 124M at 64K-128K tokens per step (A 100-600 MB) -1.4 % although
-# each GEMM alone is ahead of hipBLASLt at 64K: its persistent, statically scheduled 160 KiB-LDS
-# workgroups start late on CUs still draining the previous kernel.  Above this many A bytes the
-# engine stays on hipBLASLt.
-FGEMM_MAX_A_BYTES = int(float(os.environ.get("LLMTRAIN_FGEMM_MAX_A_MB", "64")) * 2**20)  # A/B knob
-# Ops that stay on the library GEMM at every size (outside deterministic mode's "ours" schedule)
-FGEMM_NEVER = frozenset(t for t in os.environ.get("LLMTRAIN_FGEMM_NEVER", "").split(",") if t)
-# Ops that take the fused GEMM at any A size.  dx_gelu: the MLP-projection dX with GELU backward +
-# fc-bias grad in the epilogue replaces a hipBLASLt GEMM plus a full [M, 4d] read-modify pass, and
-# wins in the whole 124M step (same-box, micro-batch 128: +0.9 %, 994.9k/995.5k vs 985.8k/986.8k
-# tok/s).  dx_attn: the attention out-projection dX with the backward's delta rows and the V-bias
-# column sums in the epilogue (deletes the delta pass; same-box mb 128: 1,076.3k vs 1,074.5k tok/s,
-# profiles/r3/ab_dx_attn_any_size_mb128.txt).  Adding the plain dX GEMMs (-0.4 %) or the forward
-# GEMMs (-1.6 %) at this size loses: hipBLASLt's 256x256 kernels run 1.1-1.3 PF on these shapes
-# against 0.86-1.14 PF for ours (profiles/r3/fgemm_wide_v2_ab_m131k.log).  With non-temporal output
-# stores at this size, fc + bias + GELU on ours beats hipBLASLt + the GELU pass alone (0.725 vs
-# 0.808 ms) but runs 0.86 ms per call inside the step and the step loses 0.4-1.0 % (qkv forward
-# too: -1.2 %; profiles/r3/nt/), so those stay on hipBLASLt.
-FGEMM_ANY_SIZE = frozenset(os.environ.get("LLMTRAIN_FGEMM_ANY", "dx_gelu,dx_attn").split(","))  # A/B knob
-
-
-_WARNED: set[str] = set()
-
-
-def _det_fallback(what: str, always: bool = False) -> None:
-    """A GEMM of a deterministic run that cannot take the hand-written fixed-order kernel (its
-    shape or alignment is outside what csrc/gemm_fused.hip takes: K % 64 == 0, K >= 256, N % 8 ==
-    0, 16-byte aligned operands) runs on hipBLASLt instead, whose split / Stream-K solutions may
-    combine partial sums in completion order.  In the "ours" schedule (every GEMM promised on our
-    kernel), and for the GEMMs the serial schedule keeps off the library (``always``), that breaks
-    the promise: say so once per distinct case instead of failing silently."""
-    if (_POLICY["gemm_all_ours"] or (always and _POLICY["deterministic"])) and what not in _WARNED:
-        _WARNED.add(what)
-        import warnings
-
-        warnings.warn(
-            f"run.deterministic: {what} cannot take the fixed-order GEMM kernel and runs on hipBLASLt "
-            "(bitwise run-to-run reproducibility of this GEMM is not guaranteed)", RuntimeWarning, stacklevel=3,
-        )
-
-
-def _det_library(what: str) -> None:
-    """Serial deterministic schedule: ``what`` runs on a tuned hipBLASLt solution by design.  Those
-    were bitwise reproducible in every repeat measured (GPT-2 124M at micro-batch 8 and 32, GPT-2 XL
-    at 32; profiles/r4/det/, profiles/r5/det/), which pins no other shape: name each such GEMM once
-    in the log, so a run on a
-    new shape knows which of its GEMMs rest on that evidence (LLMTRAIN_DET_SCHEDULE=ours moves every
-    one the kernel can take onto the fixed-order kernel)."""
-    if _POLICY["single_stream"] and what not in _WARNED:
-        _WARNED.add(what)
-        import logging
-
-        logging.getLogger(__name__).warning(
-            "run.deterministic (serial schedule): %s runs on hipBLASLt; its reproducibility is measured "
-            "for GPT-2 124M at micro-batch 8/32 and GPT-2 XL at 32 only", what,
-        )
-
-
-def _lib_mm(a: torch.Tensor, b_t: torch.Tensor, bias: torch.Tensor | None = None, *, op: str) -> torch.Tensor:
-    """``a @ b_t (+ bias)`` on the library GEMM, logged once per shape in the serial schedule."""
-    if _POLICY["single_stream"] and a.is_cuda:
-        _det_library(f"GEMM {op} M={a.shape[0]} K={a.shape[1]} N={b_t.shape[1]}")
-    return torch.mm(a, b_t) if bias is None else torch.addmm(bias, a, b_t)
-
-
-def _fgemm_ok(a: torch.Tensor, k: int, n: int, *others: torch.Tensor | None, op: str = "") -> bool:
-    """Shapes/placements the fused MFMA GEMM (csrc/gemm_fused.hip) takes and wins on:
-    K % 64 == 0, K >= 256, N % 8 == 0, 16-byte aligned operands, A small enough (see above)."""
-    if not (k % 64 == 0 and k >= 256 and n % 8 == 0):
-        _det_fallback(f"GEMM {op or 'linear'} K={k} N={n} (needs K % 64 == 0, K >= 256, N % 8 == 0)")
-        return False
-    if a.numel() * a.element_size() > FGEMM_MAX_A_BYTES and op not in FGEMM_ANY_SIZE and not _POLICY["gemm_all_ours"]:
-        return False
-    if op in FGEMM_NEVER and not _POLICY["gemm_all_ours"]:
-        return False
-    if not all(t is None or t.data_ptr() % 16 == 0 for t in (a, *others)):
-        _det_fallback(f"GEMM {op or 'linear'} with an operand not 16-byte aligned")
-        return False
-    return True
-
-
-def _fgemm_ok_any_size(a: torch.Tensor, k: int, n: int, *others: torch.Tensor | None, op: str = "") -> bool:
-    """:func:`_fgemm_ok` without the A-size routing cap (row-chunked callers: the LM head)."""
-    if not (k % 64 == 0 and k >= 256 and n % 8 == 0):
-        _det_fallback(f"GEMM {op or 'linear'} K={k} N={n} (needs K % 64 == 0, K >= 256, N % 8 == 0)", always=True)
-        return False
-    if not all(t is None or t.data_ptr() % 16 == 0 for t in (a, *others)) or a.stride(1) != 1:
-        _det_fallback(f"GEMM {op or 'linear'} with an operand not 16-byte aligned", always=True)
-        return False
-    return True
-
-
-# The hand-written GEMM's buffer descriptors and tile offsets are 32-bit byte offsets: every [M, K]
-# operand and [M, N] output must stay below 2 GiB (the binding refuses larger ones).  Larger GEMMs run
-# as row chunks (GPT-2 124M at micro-batch >= ~342, XL's d_ff = 6400 past ~168K rows), each chunk a
-# whole number of sequences for epilogue 3.
-_OFFSET_LIMIT = 2**31
-
-
-def _gemm_rows(a, b, b_kn: bool, epilogue: int, bias=None, u=None, dbias=None, seq_len: int = 0):
-    """``hip_ops().gemm_fused`` over row chunks small enough for its 32-bit offsets."""
-    m, k = a.shape
-    n = b.shape[1] if b_kn else b.shape[0]
-    align = 256 * seq_len if epilogue == 3 else 256
-    rows = max(align, (_OFFSET_LIMIT - 1) // (2 * max(k, n)) // align * align)
-    extra = () if epilogue < 3 else (seq_len,)
-    if m <= rows:
-        return tuple(hip_ops().gemm_fused(a, b, b_kn, epilogue, bias, u, dbias, *extra))
-    parts = [
-        hip_ops().gemm_fused(a[r0 : r0 + rows], b, b_kn, epilogue, bias,
-                             None if u is None else u[r0 : r0 + rows], dbias, *extra)
-        for r0 in range(0, m, rows)
-    ]
-    out = torch.cat([p[0] for p in parts])
-    if parts[0][1] is None:
-        return out, None
-    return out, torch.cat([p[1] for p in parts])
-
-
-_TUNED_BIAS_GEMMS: set[tuple[int, int, int]] | None = None
-
-
-def _library_tuned_bias_gemm(m: int, n: int, k: int) -> bool:
-    """Whether the shipped TunableOp table (llmtrain/runtime/tuned/) holds a measured library
-    solution for the bias GEMM ``[m, k] @ [n, k]^T + bias``: such shapes were timed against our
-    kernel when the table was made (micro-batch 32: qkv 0.109 vs 0.116 ms, out 0.041 vs 0.053 ms,
-    profiles/r4/mb32/) and stay on the library."""
-    global _TUNED_BIAS_GEMMS
-    if _TUNED_BIAS_GEMMS is None:
-        from ..runtime.tuning import TUNED_TABLE, tuned_gemms_active
-
-        if not tuned_gemms_active():  # not (yet) loaded in this process: nothing is routed by it
-            return False
-        shapes: set[tuple[int, int, int]] = set()
-        if TUNED_TABLE.is_file():
-            for line in TUNED_TABLE.read_text().splitlines():
-                parts = line.split(",")
-                if len(parts) >= 2 and parts[0] == "GemmAndBiasTunableOp_BFloat16_TN" and parts[1].startswith("tn_"):
-                    dims = parts[1].split("_")
-                    shapes.add((int(dims[2]), int(dims[1]), int(dims[3])))  # tn_{N}_{M}_{K}: (M, N, K)
-        _TUNED_BIAS_GEMMS = shapes
-    return (m, n, k) in _TUNED_BIAS_GEMMS
-
-
-def linear_fwd(x, w, bias=None):
-    """``x @ w^T + bias`` (nn.Linear forward, bf16 out).  GPU: the fused MFMA GEMM with the bias in
-    its epilogue where the shape allows and the library has no measured solution for it, else
-    hipBLASLt."""
-    if (_on_gpu(x) and x.dtype == torch.bfloat16 and _fgemm_ok(x, x.shape[1], w.shape[0], w, bias, op="fwd")
-            and (_POLICY["deterministic"] or bias is None
-                 or not _library_tuned_bias_gemm(x.shape[0], w.shape[0], x.shape[1]))):
-        return _gemm_rows(x, w, False, 0, bias)[0]
-    return _lib_mm(x, w.t(), bias, op="fwd")
-
-
-def linear_fwd_gelu(x, w, bias=None):
-    """``u = x @ w^T + bias`` and ``g = gelu(u)`` (exact erf GELU of the bf16 ``u``, which the
-    backward reads): on GPU the GELU rides in the GEMM epilogue, no separate pass over ``u``."""
-    if _on_gpu(x) and x.dtype == torch.bfloat16 and _fgemm_ok(x, x.shape[1], w.shape[0], w, bias, op="fwd_gelu"):
-        u, g = _gemm_rows(x, w, False, 1, bias)
-        return u, g
-    u = _lib_mm(x, w.t(), bias, op="fc fwd")
-    return u, gelu_fwd(u)
-
-
-def linear_fwd_gelu_gd(x, w, bias=None):
-    """``gd = gelu'(u)`` and ``g = gelu(u)`` of ``u = x @ w^T + bias`` (the bf16 ``u``, as the
-    backward would read it): the fc forward keeps the GELU derivative instead of the
-    pre-activation, so the MLP-projection dX epilogue (:func:`linear_dx_gd`) multiplies by a stored
-    value instead of evaluating erf per element.  GPU: one fused-GEMM epilogue (4) at any size;
-    shapes that kernel does not take form ``u`` on the library and the two maps with torch ops."""
-    if (_on_gpu(x) and x.dtype == torch.bfloat16 and _fgemm_ok_any_size(x, x.shape[1], w.shape[0], w, bias,
-                                                                     op="fc fwd + GELU'")):
-        gd, g = _gemm_rows(x, w, False, 4, bias)
-        return gd, g
-    u = _lib_mm(x, w.t(), bias, op="fc fwd") if _on_gpu(x) else (
-        torch.mm(x, w.t()) if bias is None else torch.addmm(bias, x, w.t()))
-    return ref.gelu_grad(u), gelu_fwd(u)
-
-
-def linear_dx_gd(dy, w, gd, dbias=None):
-    """``du = (dy @ w) * gd`` and ``dbias += colsum(du)`` with ``gd = gelu'(u)`` stored by
-    :func:`linear_fwd_gelu_gd`: the MLP-projection data gradient and the GELU backward in one GEMM
-    epilogue (5) on GPU."""
-    if _on_gpu(dy) and dy.dtype == torch.bfloat16 and _fgemm_ok_any_size(dy, dy.shape[1], w.shape[1], w, gd,
-                                                                         op="MLP-projection dX * gelu'"):
-        return _gemm_rows(dy, w, True, 5, None, gd, dbias)[0]
-    dg = _lib_mm(dy, w, op="MLP-projection dX") if _on_gpu(dy) else torch.mm(dy, w)
-    du = (dg.float() * gd.float()).to(dy.dtype)
-    if dbias is not None:
-        colsum_accum(du, dbias)
-    return du
-
-
-def linear_dx(dy, w):
-    """``dy @ w`` (data gradient of nn.Linear with weight ``w [out, in]``)."""
-    if _on_gpu(dy) and dy.dtype == torch.bfloat16 and _fgemm_ok(dy, dy.shape[1], w.shape[1], w, op="dx"):
-        return _gemm_rows(dy, w, True, 0)[0]
-    return _lib_mm(dy, w, op="dX")
-
-
-# rows per launch of the LM-head GEMMs on the hand-written kernel: its buffer descriptors take
-# 32-bit byte offsets, and [rows, 50304] bf16 must stay below 2 GiB
-_HEAD_ROWS = 16384
-
-
-def head_logits(h, w):
-    """``logits = h @ w^T`` for the vocab-padded LM head ``w [Vp, d]``: hipBLASLt on the fast path;
-    in deterministic mode (either schedule) row chunks of the hand-written fixed-order kernel,
-    written in place into one ``[M, Vp]`` output.  The library's tuned solution for this shape is a
-    Stream-K kernel (``SK3``), which combines partial tiles in completion order — the one library
-    GEMM left in the serial schedule when its bitwise guarantee failed once
-    (profiles/r5/det/pytest_gpu_serial_divergence.txt, docs/round6.md §2)."""
-    if not (_on_gpu(h) and _POLICY["deterministic"] and h.dtype == torch.bfloat16
-            and _fgemm_ok_any_size(h, h.shape[1], w.shape[0], w, op="LM-head logits")):
-        return _lib_mm(h, w.t(), op="LM-head logits")
-    out = torch.empty(h.shape[0], w.shape[0], dtype=h.dtype, device=h.device)
-    for r0 in range(0, h.shape[0], _HEAD_ROWS):
-        r1 = min(h.shape[0], r0 + _HEAD_ROWS)
-        hip_ops().gemm_fused(h[r0:r1], w, False, 0, None, None, None, 0, out[r0:r1])
-    return out
-
-
-def head_dx(dlogits, w):
-    """``dh = dlogits @ w`` (LM-head data gradient, ``w [Vp, d]``), row-chunked like
-    :func:`head_logits` on our kernel.  Deterministic mode always takes our kernel here: this is the
-    step's only GEMM with a 50304-deep reduction, where the library picks split / Stream-K
-    solutions whose partial sums combine in completion order — the one run-to-run difference left
-    in the serial schedule (bench/determinism_probe.py at micro-batch 8: the gradients first differ
-    at ln_f, the head dX's output)."""
-    k, n = dlogits.shape[1], w.shape[1]
-    if not (_on_gpu(dlogits) and _POLICY["deterministic"] and dlogits.dtype == torch.bfloat16
-            and k % 64 == 0 and k >= 256 and n % 8 == 0  # the size cap does not apply: row chunks
-            and dlogits.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and dlogits.stride(1) == 1):
-        if _on_gpu(dlogits) and _POLICY["deterministic"]:
-            _det_fallback(f"LM-head dX K={k} N={n}", always=True)
-        return torch.mm(dlogits, w)
-    out = torch.empty(dlogits.shape[0], w.shape[1], dtype=dlogits.dtype, device=dlogits.device)
-    for r0 in range(0, dlogits.shape[0], _HEAD_ROWS):
-        r1 = min(dlogits.shape[0], r0 + _HEAD_ROWS)
-        hip_ops().gemm_fused(dlogits[r0:r1], w, True, 0, None, None, None, 0, out[r0:r1])
-    return out
-
-
-def linear_dx_gelu_bwd(dy, w, u, dbias=None):
-    """``du = (dy @ w) * gelu'(u)`` and ``dbias += colsum(du)``: the data gradient of the MLP
-    projection fused with the GELU backward and the fc bias gradient (one GEMM epilogue on GPU
-    instead of a GEMM plus a full read-modify pass over the [M, d_ff] activations)."""
-    if _on_gpu(dy) and dy.dtype == torch.bfloat16 and _fgemm_ok(dy, dy.shape[1], w.shape[1], w, u, op="dx_gelu"):
-        return _gemm_rows(dy, w, True, 2, None, u, dbias)[0]
-    return gelu_bwd(_lib_mm(dy, w, op="MLP-projection dX"), u, dbias)
-
-
-def linear_dx_attn(dy, w, att, seqlen: int, v_bias_grad=None, head_dim: int = 64):
-    """Data gradient of the attention output projection, ``dO = dy @ w``, plus the flash-attention
-    backward's row constants ``delta[b, h, t] = sum_d dO * O`` (``att`` = the attention output O)
-    and, when given, ``v_bias_grad += colsum(dO)`` (the V part of the qkv bias gradient, valid
-    without attention dropout).  GPU: one fused GEMM epilogue (csrc/gemm_fused.hip, epilogue 3)
-    replacing the separate pass that re-read dO and O.  Returns ``(dO, delta)``; ``delta`` is None
-    when the GEMM is not taken (the attention backward then computes it itself, and the caller
-    must leave ``v_bias_grad`` to it)."""
-    if (
-        _on_gpu(dy)
-        and dy.dtype == torch.bfloat16
-        and head_dim == 64  # the epilogue's per-head row dots are 64 columns wide
-        and dy.shape[0] % seqlen == 0
-        and w.shape[1] % 64 == 0
-        and _fgemm_ok(dy, dy.shape[1], w.shape[1], w, att, op="dx_attn")
-    ):
-        return _gemm_rows(dy, w, True, 3, None, att, v_bias_grad, seqlen)
-    if _on_gpu(dy) and head_dim != 64:
-        # the epilogue's row dots need 64-wide heads: a plain dX GEMM (fixed-order kernel where the
-        # shape allows, e.g. the reference presets' d = 256 / 384) and attn_bwd forms delta itself
-        return linear_dx(dy, w), None
-    return _lib_mm(dy, w, op="attention out-projection dX"), None
-
-
-def wgrad_accum(dst, dy, x, *, bias=None) -> None:
-    """``dst (fp32 [N, K]) += dy[M, N]^T @ x[M, K]`` and, with ``bias`` (fp32 ``[N]``),
-    ``bias += colsum(dy)`` — the weight and bias gradients of an nn.Linear whose output gradient
-    is ``dy`` (``dy`` may be a column slice with a larger row stride).  GPU: the split-K MFMA GEMM
-    of csrc/gemm_wgrad_pp.hip with the bias column sums fused."""
-    if _on_gpu(dst):
-        hip_ops().wgrad_gemm_pp(dy, x, dst, bias, 0, -1)
-        return
-    dst.addmm_(dy.t().float(), x.float())
-    if bias is not None:
-        colsum_accum(dy, bias)
 
 
 def sumsq(x):

@@ -16,7 +16,7 @@ from pathlib import Path
 
 import torch
 
-__all__ = ["EXT_PATH", "is_loaded", "load", "require"]
+__all__ = ["EXT_PATH", "hip_ops", "is_loaded", "load", "require"]
 
 EXT_PATH = Path(__file__).with_name("_llmtrain_hip.so")
 DEBUG_EXT_PATH = Path(__file__).with_name("_llmtrain_hip_debug.so")
@@ -53,3 +53,8 @@ def require() -> None:
     """Raise unless the HIP extension is loaded (called before any GPU kernel launch)."""
     if not load():
         raise RuntimeError(f"llmtrain HIP extension unavailable: {_state['error']}")
+
+
+def hip_ops():  # noqa: ANN201 - torch op namespace
+    require()
+    return torch.ops.llmtrain_hip

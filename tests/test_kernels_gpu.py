@@ -521,6 +521,65 @@ def test_gemm_fused_attn_dx_delta(gpu_device, M, N, K, T, b_kn):
     _close(dbias, ref_b, 1e-3 + 1e-5 * ref_b.abs().max().item(), 1e-4, "dbias_v")
 
 
+# ---- row chunks of the fused GEMM (llmtrain.ops.gemm.run_gemm) ----------------------------------
+# A lowered offset limit forces, at a small shape, the chunking that 2 GiB operands need; the
+# chunked call must give what the single launch of the same call gives.
+def test_gemm_chunks_plain_in_place(gpu_device):
+    """Plain NT GEMM + bias in 256-row chunks (three full, one ragged of 232), written in place
+    into a row slice of a larger tensor: the LM-head path."""
+    from llmtrain.ops import gemm
+
+    M, N, K = 1000, 200, 256
+    a, w, b, bias = _gemm_operands(M, N, K, False, gpu_device, 21)
+    limit = 2 * 256 * 256 + 1
+    assert len(gemm.row_chunks(M, K, N, gemm.Epilogue.BIAS, offset_limit=limit)) == 4
+    single, _ = gemm.run_gemm(gemm.HEAD_LOGITS, a, b, bias)
+    big = torch.full((M + 16, N), 7.0, device=gpu_device, dtype=torch.bfloat16)
+    out, none = gemm.run_gemm(gemm.HEAD_LOGITS, a, b, bias, out=big[8 : 8 + M], offset_limit=limit)
+    assert none is None and out.data_ptr() == big[8].data_ptr()
+    assert torch.equal(out, single)
+    assert torch.all(big[:8] == 7.0) and torch.all(big[8 + M :] == 7.0)
+    fresh, _ = gemm.run_gemm(gemm.FWD, a, b, bias, offset_limit=limit)  # no out=: one new [M, N] tensor
+    assert torch.equal(fresh, single)
+
+
+def test_gemm_chunks_stored_gelu_grad(gpu_device):
+    """NN GEMM * stored gelu'(u) with the bias column sums, in 256-row chunks of ``dy`` and ``gd``."""
+    from llmtrain.ops import gemm
+
+    M, N, K = 1000, 200, 256
+    dy, w, b, _ = _gemm_operands(M, N, K, True, gpu_device, 22)
+    g = torch.Generator(device="cpu").manual_seed(23)
+    gd = torch.rand(M, N, generator=g).to(gpu_device, torch.bfloat16)
+    db1, dbc = torch.full((N,), 0.5, device=gpu_device), torch.full((N,), 0.5, device=gpu_device)
+    single, _ = gemm.run_gemm(gemm.DX_GD, dy, b, None, gd, db1)
+    du, none = gemm.run_gemm(gemm.DX_GD, dy, b, None, gd, dbc, offset_limit=2 * 256 * 256 + 1)
+    assert none is None and torch.equal(du, single)
+    _close(du, (dy.float() @ w.float().t()) * gd.float(), 2e-2, 1e-2, "du")
+    # fp32 additions across chunks associate differently from one launch's: close, not bitwise
+    _close(dbc, 0.5 + du.float().sum(0), 1e-3, 1e-4, "dbias over chunks")
+    _close(db1, 0.5 + du.float().sum(0), 1e-3, 1e-4, "dbias, one launch")
+
+
+def test_gemm_chunks_attn_delta(gpu_device):
+    """Attention-delta epilogue in chunks of whole sequences (two of 256 sequences, one of 128)."""
+    from llmtrain.ops import gemm
+
+    M, N, K, T = 40960, 256, 256, 64
+    dy, w, b, _ = _gemm_operands(M, N, K, True, gpu_device, 24)
+    g = torch.Generator(device="cpu").manual_seed(25)
+    o = torch.randn(M, N, generator=g).to(gpu_device, torch.bfloat16)
+    limit = 2 * 256 * 16384 + 1
+    assert gemm.row_chunks(M, K, N, gemm.Epilogue.ATTN_DELTA, T, offset_limit=limit) == [
+        (0, 16384), (16384, 32768), (32768, M)]
+    db1, dbc = torch.full((N,), 0.25, device=gpu_device), torch.full((N,), 0.25, device=gpu_device)
+    do1, delta1 = gemm.run_gemm(gemm.DX_ATTN, dy, b, None, o, db1, seq_len=T)
+    do, delta = gemm.run_gemm(gemm.DX_ATTN, dy, b, None, o, dbc, seq_len=T, offset_limit=limit)
+    assert delta.shape == (M // T, N // 64, T)
+    assert torch.equal(do, do1) and torch.equal(delta, delta1)
+    _close(dbc, 0.25 + do.float().sum(0), 1e-3, 1e-4, "dbias_v over chunks")
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_scale_device_scalar(gpu_device, dtype):
     """``scale``: x * s with s read from device memory, fp32 math and one rounding — matches the

@@ -25,7 +25,7 @@ def test_cpu_device_is_a_no_op() -> None:
 def test_tuned_bias_gemm_shapes_route_to_the_library(monkeypatch) -> None:
     """Bias-GEMM shapes with a measured library solution in the table (micro-batch 32 qkv / out
     forward) are routed away from the fused GEMM; other shapes and an unloaded table are not."""
-    import llmtrain.ops as ops
+    from llmtrain.ops import gemm as ops
     from llmtrain.runtime import tuning
 
     monkeypatch.setattr(ops, "_TUNED_BIAS_GEMMS", None)
