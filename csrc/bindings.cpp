@@ -78,7 +78,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> add_layernorm_fwd(const Tensor& x, co
   TORCH_CHECK(x.dim() == 2, "x must be [M, d]");
   const int64_t M = x.size(0), d = x.size(1);
   TORCH_CHECK(w.numel() == d && b.numel() == d, "weight/bias must have d elements");
-  TORCH_CHECK(d % 4 == 0 && d <= 2048, "LayerNorm kernel needs d % 4 == 0 and d <= 2048");
+  TORCH_CHECK(d % 4 == 0 && d <= llmt::kLnMaxD, "LayerNorm kernel needs d % 4 == 0 and d <= ", llmt::kLnMaxD);
   TORCH_CHECK(out_dtype == at::kBFloat16 || out_dtype == at::kFloat, "out_dtype must be bf16 or f32");
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   llmt::LnFwdArgs a{};
@@ -123,7 +123,7 @@ std::tuple<Tensor, Tensor, Tensor> layernorm_bwd_impl(const Tensor& dy, const Te
   TORCH_CHECK(xs.scalar_type() == at::kFloat || xs.scalar_type() == at::kBFloat16, "xs must be f32 or bf16");
   TORCH_CHECK(dy.sizes() == xs.sizes() && xs.dim() == 2, "dy/xs must be [M, d]");
   const int64_t M = xs.size(0), d = xs.size(1);
-  TORCH_CHECK(d % 4 == 0 && d <= 2048, "LayerNorm kernel needs d % 4 == 0 and d <= 2048");
+  TORCH_CHECK(d % 4 == 0 && d <= llmt::kLnMaxD, "LayerNorm kernel needs d % 4 == 0 and d <= ", llmt::kLnMaxD);
   for (const Tensor* t : {&mean, &rstd}) {
     check_gpu(*t, "mean/rstd");
     check_dtype(*t, at::kFloat, "mean/rstd");

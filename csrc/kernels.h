@@ -23,8 +23,12 @@ struct DropoutArgs {
   const uint32_t* seed_add = nullptr;
 };
 
+// widest row the LayerNorm kernels take (d % 4 == 0): one wave per row up to 2048 columns, one
+// workgroup per row above
+constexpr int kLnMaxD = 8192;
+
 struct LnFwdArgs {
-  const void* x;       // [M, d] residual stream (f32, or bf16 with x_bf16)
+  const void* x;      // [M, d] residual stream (f32, or bf16 with x_bf16)
   bool x_bf16;
   const void* delta;   // [M, d] optional update added to x (bf16 or f32)
   bool delta_bf16;

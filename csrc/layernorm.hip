@@ -4,7 +4,9 @@
 // residual adds at :100/:104-105.  One wave64 owns one row of width d; each lane keeps its
 // ceil(d / 256) float4 chunks of the row in registers, so the statistics need no second read
 // (mean and variance are two in-register passes).  Memory bound: the kernels move 12 B/elem
-// (forward: x f32 + delta bf16 in, x' f32 + y bf16 out) and 16 B/elem (backward).
+// (forward: x f32 + delta bf16 in, x' f32 + y bf16 out) and 16 B/elem (backward).  Rows wider
+// than 2048 columns (up to kLnMaxD = 8192) give a whole workgroup one row instead: the *_wide
+// kernels below, same contracts.
 //
 // Backward accumulates dgamma/dbeta (and optionally the column sum of dx, which is the bias
 // gradient of the projection whose output was added into this residual stream) with per-lane
@@ -409,6 +411,224 @@ __global__ __launch_bounds__(256, 3) void ln_bwd_split_kernel(
   }
 }
 
+// ---- rows wider than 2048 columns (2048 < d <= 8192): one WORKGROUP owns a row ---------------------
+// A row's d / 4 float4 chunks are dealt round-robin over all NW * 64 threads (chunk c = tid + j * NT,
+// so every load instruction of the workgroup covers one contiguous, fully coalesced span) and each
+// thread keeps its CPT chunks in registers; wave sums meet through a few words of LDS.  Waves x
+// chunks per width class K (d <= 3072, 4096, 6144, 8192), chosen so that no instantiation spills
+// (register counts and occupancy: docs/performance.md):
+//   forward   4 x 3, 4 x 4, 8 x 3, 8 x 4   (4 live arrays; 80-104 VGPRs)
+//   backward  4 x 3 at 3 waves / SIMD, then 8 x 2, 16 x 2, 16 x 2 at 4 waves / SIMD (7 live arrays:
+//             three or four chunks per thread do not fit 128 VGPRs, so wider rows take more threads)
+template <int K>
+struct LnWide {
+  static_assert(K >= 0 && K < 4, "width class");
+  static constexpr int kFwd[4][2] = {{4, 3}, {4, 4}, {8, 3}, {8, 4}};
+  static constexpr int kBwd[4][3] = {{4, 3, 3}, {8, 2, 4}, {16, 2, 4}, {16, 2, 4}};
+  static constexpr int FNW = kFwd[K][0], FCPT = kFwd[K][1];                      // forward waves, chunks
+  static constexpr int BNW = kBwd[K][0], BCPT = kBwd[K][1], BOCC = kBwd[K][2];  // backward, + waves / SIMD
+};
+
+// sum over the workgroup of one value per thread: fixed order (wave 0, 1, ...), the same value in
+// every thread.  The caller separates two uses of one `slot` array by a barrier on another.
+template <int NW>
+__device__ __forceinline__ float wide_sum(float v, float* slot, int lane, int wid) {
+  v = wave_sum(v);
+  if (lane == 0) slot[wid] = v;
+  __syncthreads();
+  float r = 0.f;
+#pragma unroll
+  for (int k = 0; k < NW; ++k) r += slot[k];
+  return r;
+}
+
+// add_ln_fwd_kernel's contract for a wide row.  Persistent: gamma / beta are loaded once and the
+// workgroup strides over rows.  Loads as in the narrow kernel: unconditional, all of a row issued
+// before the first wait, threads past the row end read column 0 and are zeroed.
+template <int NW, int CPT, typename TD, typename TY, typename TX>
+__global__ __launch_bounds__(NW * 64) void add_ln_fwd_wide_kernel(
+    const TX* __restrict__ x, const TD* __restrict__ delta, const float* __restrict__ w,
+    const float* __restrict__ b, TX* __restrict__ xs_out, TY* __restrict__ y,
+    float* __restrict__ mean_out, float* __restrict__ rstd_out, int M, int d, float eps, DropoutArgs dr) {
+  resolve_dropout(dr);
+  constexpr int NT = NW * 64;
+  // two slot arrays: a row's barrier on one separates the other's read from its next write
+  __shared__ float red_s[NW], red_q[NW];
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nc = d >> 2;
+  const float inv_d = 1.f / (float)d;
+  float4_t ww[CPT], bb[CPT];
+#pragma unroll
+  for (int j = 0; j < CPT; ++j) {
+    const int c = tid + j * NT, cc = c < nc ? c : 0;
+    ww[j] = load4(w + 4 * cc);
+    bb[j] = load4(b + 4 * cc);
+  }
+  for (long row = blockIdx.x; row < M; row += gridDim.x) {  // uniform over the workgroup
+    const TX* xr = x + row * d;
+    float4_t v[CPT], dv[CPT];
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+      const int c = tid + j * NT, cc = c < nc ? c : 0;
+      v[j] = load4(xr + 4 * cc);
+    }
+    if (delta != nullptr) {
+#pragma unroll
+      for (int j = 0; j < CPT; ++j) {
+        const int c = tid + j * NT, cc = c < nc ? c : 0;
+        dv[j] = load4(delta + row * d + 4 * cc);
+      }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+      const int c = tid + j * NT;
+      if (delta != nullptr) {
+        if (dr.thr != 0) {  // residual-branch dropout, element index row * d + column as everywhere
+          const uint64_t e0 = (uint64_t)row * d + 4 * c;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) dv[j][t] = drop_keep(dr.seed, dr.thr, e0 + t) ? dv[j][t] * dr.scale : 0.f;
+        }
+        v[j] += dv[j];
+        if (!std::is_same<TX, float>::value) v[j] = round_bf16x4(v[j]);
+        if (c < nc) store4(xs_out + row * d + 4 * c, v[j]);
+      }
+      if (c >= nc) v[j] = float4_t{0.f, 0.f, 0.f, 0.f};
+      s += v[j][0] + v[j][1] + v[j][2] + v[j][3];
+    }
+    const float mu = wide_sum<NW>(s, red_s, lane, wid) * inv_d;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+      const int c = tid + j * NT;
+      if (c < nc) {
+        float4_t t = v[j] - mu;
+        q += t[0] * t[0] + t[1] * t[1] + t[2] * t[2] + t[3] * t[3];
+      }
+    }
+    const float rs = rsqrtf(wide_sum<NW>(q, red_q, lane, wid) * inv_d + eps);
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+      const int c = tid + j * NT;
+      const float4_t out = (v[j] - mu) * rs * ww[j] + bb[j];
+      if (c < nc) store4(y + row * d + 4 * c, out);
+    }
+    if (tid == 0) {
+      mean_out[row] = mu;
+      rstd_out[row] = rs;
+    }
+  }
+}
+
+// ln_bwd_split_kernel's contract for a wide row: one row per workgroup iteration, so every column
+// belongs to exactly one thread for the whole launch and the dw / db / dproj column partials stay in
+// that thread's registers (no d-sized LDS, no atomics) and go straight to this workgroup's partial
+// rows of the workspace at the end.  The two row sums meet in LDS, one barrier per row, parity
+// double-buffered.  Summation order is fixed throughout: bitwise reproducible.
+template <int NW, int CPT, int OCC, typename TDY, bool LOWP_OUT, typename TX, typename TG>
+__global__ __launch_bounds__(NW * 64, OCC) void ln_bwd_wide_kernel(
+    const TDY* __restrict__ dy, const TX* __restrict__ xs, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ w, const TG* __restrict__ dresid,
+    const float* __restrict__ dy_scale, TG* __restrict__ dx, TDY* __restrict__ dx_lp,
+    float* __restrict__ dw, float* __restrict__ db, float* __restrict__ dproj, int M, int d, DropoutArgs dr) {
+  resolve_dropout(dr);
+  constexpr int NT = NW * 64;
+  __shared__ float red[2][NW][2];  // [parity][wave][s1|s2]
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nc = d >> 2;
+  const float scale = dy_scale != nullptr ? *dy_scale : 1.f;
+  const float inv_d = 1.f / (float)d;
+  const bool has_pp = dproj != nullptr;
+  const float4_t zero = {0.f, 0.f, 0.f, 0.f};
+
+  float4_t pw[CPT], pb[CPT], pp[CPT], gam[CPT];
+  unsigned off[CPT];  // this thread's columns: 32-bit offsets from the (uniform) row pointers
+#pragma unroll
+  for (int j = 0; j < CPT; ++j) {
+    pw[j] = zero; pb[j] = zero; pp[j] = zero;
+    const int c = tid + j * NT;
+    off[j] = 4u * (unsigned)(c < nc ? c : 0);
+    gam[j] = load4(w + off[j]);
+  }
+
+  int par = 0;
+  for (long row = blockIdx.x; row < M; row += gridDim.x, par ^= 1) {  // uniform over the workgroup
+    const float mu = mean[row], rs = rstd[row];
+    const TDY* dyr = dy + row * d;
+    const TX* xr = xs + row * d;
+    const TG* rrow = dresid + row * d;
+    TG* dxr = dx + row * d;
+    TDY* lpr = dx_lp + row * d;
+    float4_t g[CPT], xh[CPT], rr[CPT];
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+      g[j] = load4(dyr + off[j]);
+      xh[j] = load4_nt(xr + off[j]);
+    }
+    if (dresid != nullptr) {
+#pragma unroll
+      for (int j = 0; j < CPT; ++j) rr[j] = load4_nt(rrow + off[j]);
+    }
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+      const bool ok = tid + j * NT < nc;
+      g[j] = ok ? g[j] * scale : zero;
+      xh[j] = ok ? (xh[j] - mu) * rs : zero;
+      float4_t gw = g[j] * gam[j];
+      s1 += gw[0] + gw[1] + gw[2] + gw[3];
+      float4_t gx = gw * xh[j];
+      s2 += gx[0] + gx[1] + gx[2] + gx[3];
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    if (lane == 0) {
+      red[par][wid][0] = s1;
+      red[par][wid][1] = s2;
+    }
+    __syncthreads();
+    float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+      c1 += red[par][k][0];
+      c2 += red[par][k][1];
+    }
+    c1 *= inv_d;
+    c2 *= inv_d;
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+      const int c = tid + j * NT;
+      float4_t out = (g[j] * gam[j] - c1 - xh[j] * c2) * rs;
+      if (dresid != nullptr) out += rr[j];
+      float4_t br = out;
+      if (dr.thr != 0) {
+        const uint64_t e0 = (uint64_t)row * d + 4 * c;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) br[t] = drop_keep(dr.seed, dr.thr, e0 + t) ? out[t] * dr.scale : 0.f;
+      }
+      pw[j] += g[j] * xh[j];  // zero past the row end
+      pb[j] += g[j];
+      if (c < nc) {
+        store4_nt(dxr + off[j], out);
+        if (LOWP_OUT) store4(lpr + off[j], br);
+        if (has_pp) pp[j] += br;
+      }
+    }
+  }
+
+  // this workgroup's partial rows: each column written by the one thread that owns it
+  const long prow = (long)blockIdx.x * d;
+#pragma unroll
+  for (int j = 0; j < CPT; ++j) {
+    const int c = tid + j * NT;
+    if (c < nc) {
+      store4(dw + prow + off[j], pw[j]);
+      store4(db + prow + off[j], pb[j]);
+      if (has_pp) store4(dproj + prow + off[j], pp[j]);
+    }
+  }
+}
+
 template <int MAXC, typename TX>
 void launch_fwd_x(const LnFwdArgs& a, hipStream_t st) {
   const long wgs = (a.M + kLnWaves - 1) / kLnWaves;
@@ -429,6 +649,29 @@ template <int MAXC>
 void launch_fwd_c(const LnFwdArgs& a, hipStream_t st) {
   if (a.x_bf16) launch_fwd_x<MAXC, bf16_raw>(a, st);
   else launch_fwd_x<MAXC, float>(a, st);
+}
+
+// wide rows: one row per workgroup, at most 32 waves' worth of workgroups per CU (8 x CUs of 4
+// waves, 4 x CUs of 8), as the persistent narrow forward
+template <typename S, typename TX>
+void launch_fwd_wide_x(const LnFwdArgs& a, hipStream_t st) {
+  dim3 grid((unsigned)std::min<long>(a.M, (32L / S::FNW) * device_cu_count())), block(S::FNW * 64);
+#define LN_FWD(TD, TY)                                                                                  \
+  hipLaunchKernelGGL((add_ln_fwd_wide_kernel<S::FNW, S::FCPT, TD, TY, TX>), grid, block, 0, st,         \
+                     (const TX*)a.x, (const TD*)a.delta, a.w, a.b, (TX*)a.xs_out, (TY*)a.y, a.mean, a.rstd, \
+                     a.M, a.d, a.eps, a.dropout)
+  if (a.delta_bf16) {
+    if (a.y_bf16) LN_FWD(bf16_raw, bf16_raw); else LN_FWD(bf16_raw, float);
+  } else {
+    if (a.y_bf16) LN_FWD(float, bf16_raw); else LN_FWD(float, float);
+  }
+#undef LN_FWD
+}
+
+template <typename S>
+void launch_fwd_wide(const LnFwdArgs& a, hipStream_t st) {
+  if (a.x_bf16) launch_fwd_wide_x<S, bf16_raw>(a, st);
+  else launch_fwd_wide_x<S, float>(a, st);
 }
 
 // The backward kernel for this row width: the split-row kernel above 768 columns (GPT-2 XL
@@ -477,14 +720,11 @@ int bwd_grid_c(const LnBwdArgs& a) {
   return stride_grid((long long)(a.M + kBwdWaves - 1) / kBwdWaves, 1, cap);
 }
 
-template <int MAXC>
-void launch_bwd_c(const LnBwdArgs& a, hipStream_t st) {
-  const size_t shm = (size_t)kBwdWaves * a.d * sizeof(float);
-  const int grid = bwd_grid_c<MAXC>(a);
+// the backward's launch, partial rows and (unless deferred) column reduce, shared by every kernel
+void launch_bwd_fn(const void* fn, int grid, int threads, size_t shm, const LnBwdArgs& a, hipStream_t st) {
   float* pw = a.ws;
   float* pb = a.ws + (long)grid * a.d;
   float* pp = a.dproj != nullptr ? a.ws + 2L * grid * a.d : nullptr;
-  const void* fn = bwd_kernel<MAXC>(a);
   const void* dy = a.dy;
   void* dx_lp = a.dx_lp;
   const void *xs = a.xs, *dresid = a.dresid;
@@ -493,7 +733,7 @@ void launch_bwd_c(const LnBwdArgs& a, hipStream_t st) {
   int M = a.M, d = a.d;
   DropoutArgs dr = a.dropout;
   void* args[] = {&dy, &xs, &mean, &rstd, &w, &dresid, &dy_scale, &dx, &dx_lp, &pw, &pb, &pp, &M, &d, &dr};
-  (void)hipLaunchKernel(fn, dim3(grid), dim3(256), args, shm, st);
+  (void)hipLaunchKernel(fn, dim3(grid), dim3(threads), args, shm, st);
 
   if (a.defer_params) return;  // the caller reduces dw / db later, batched with other LayerNorms
   const int nacc = a.dproj != nullptr ? 3 : 2;
@@ -503,69 +743,100 @@ void launch_bwd_c(const LnBwdArgs& a, hipStream_t st) {
   launch_colsum_reduce_multi(parts, dst, nacc, grid, a.d, scratch, st);
 }
 
+template <int MAXC>
+void launch_bwd_c(const LnBwdArgs& a, hipStream_t st) {
+  launch_bwd_fn(bwd_kernel<MAXC>(a), bwd_grid_c<MAXC>(a), 256, (size_t)kBwdWaves * a.d * sizeof(float), a, st);
+}
+
+// ---- wide rows -----------------------------------------------------------------------------------
+template <typename S, typename TDY, bool LP>
+const void* bwd_wide_r(int mode) {
+  if (mode == 2) return (const void*)&ln_bwd_wide_kernel<S::BNW, S::BCPT, S::BOCC, TDY, LP, bf16_raw, bf16_raw>;
+  if (mode == 1) return (const void*)&ln_bwd_wide_kernel<S::BNW, S::BCPT, S::BOCC, TDY, LP, float, bf16_raw>;
+  return (const void*)&ln_bwd_wide_kernel<S::BNW, S::BCPT, S::BOCC, TDY, LP, float, float>;
+}
+
+template <typename S>
+const void* bwd_wide_kernel(const LnBwdArgs& a) {
+  if (a.dy_bf16) return a.dx_lp != nullptr ? bwd_wide_r<S, bf16_raw, true>(res_mode(a)) : bwd_wide_r<S, bf16_raw, false>(res_mode(a));
+  return a.dx_lp != nullptr ? (const void*)&ln_bwd_wide_kernel<S::BNW, S::BCPT, S::BOCC, float, true, float, float>
+                            : (const void*)&ln_bwd_wide_kernel<S::BNW, S::BCPT, S::BOCC, float, false, float, float>;
+}
+
+// One row per workgroup iteration and one resident round of workgroups, the kernel's launch bound:
+// 3 x CUs workgroups of 4 waves, 2 x CUs of 8, 1 x CUs of 16; a function of (M, d) alone.  The cap
+// also bounds the workspace's [dw | db | dproj][grid][d] partial rows: on 256 CUs at most
+// 3 x 768 x 3072 x 4 B = 27 MiB at d = 3072, 3 x 512 x 4096 x 4 B = 24 MiB at d = 4096 and
+// 3 x 256 x 8192 x 4 B = 24 MiB at d = 8192 (two thirds of that without dproj).
+template <typename S>
+int bwd_grid_wide(const LnBwdArgs& a) {
+  return stride_grid(a.M, 1, (S::BOCC * 4 / S::BNW) * device_cu_count());
+}
+
+// ---- row width -> kernel family, the one place that knows the widths ------------------------------
+template <int MAXC>
+struct LnNarrow {};  // one wave per row, MAXC = ceil(d / 256) chunks per lane (d <= 2048)
+
+template <int MAXC> void launch_fwd(LnNarrow<MAXC>, const LnFwdArgs& a, hipStream_t st) { launch_fwd_c<MAXC>(a, st); }
+template <int MAXC> void launch_bwd(LnNarrow<MAXC>, const LnBwdArgs& a, hipStream_t st) { launch_bwd_c<MAXC>(a, st); }
+template <int MAXC> int bwd_grid(LnNarrow<MAXC>, const LnBwdArgs& a) { return bwd_grid_c<MAXC>(a); }
+
+template <int K> void launch_fwd(LnWide<K>, const LnFwdArgs& a, hipStream_t st) { launch_fwd_wide<LnWide<K>>(a, st); }
+template <int K> void launch_bwd(LnWide<K>, const LnBwdArgs& a, hipStream_t st) {
+  using S = LnWide<K>;
+  launch_bwd_fn(bwd_wide_kernel<S>(a), bwd_grid_wide<S>(a), S::BNW * 64, 0, a, st);
+}
+template <int K> int bwd_grid(LnWide<K>, const LnBwdArgs& a) { return bwd_grid_wide<LnWide<K>>(a); }
+
+// calls f(shape tag) for the kernels that take rows of d columns; false when no kernel does
+template <typename F>
+bool ln_dispatch(int d, F&& f) {
+  if (d <= 0 || d % 4 != 0 || d > kLnMaxD) return false;
+  const int nc = d / 4;
+  if (nc <= 512) {
+    switch ((nc + 63) / 64) {
+      case 1: f(LnNarrow<1>{}); break;
+      case 2: f(LnNarrow<2>{}); break;
+      case 3: f(LnNarrow<3>{}); break;
+      case 4: f(LnNarrow<4>{}); break;
+      case 5: f(LnNarrow<5>{}); break;
+      case 6: f(LnNarrow<6>{}); break;
+      case 7: f(LnNarrow<7>{}); break;
+      default: f(LnNarrow<8>{}); break;
+    }
+  } else if (nc <= 768) {
+    f(LnWide<0>{});
+  } else if (nc <= 1024) {
+    f(LnWide<1>{});
+  } else if (nc <= 1536) {
+    f(LnWide<2>{});
+  } else {
+    f(LnWide<3>{});
+  }
+  return true;
+}
+
 }  // namespace
 
-#define LN_DISPATCH(FN, ARGS, ST)                      \
-  switch ((ARGS.d / 4 + 63) / 64) {                    \
-    case 1: FN<1>(ARGS, ST); break;                    \
-    case 2: FN<2>(ARGS, ST); break;                    \
-    case 3: FN<3>(ARGS, ST); break;                    \
-    case 4: FN<4>(ARGS, ST); break;                    \
-    case 5: FN<5>(ARGS, ST); break;                    \
-    case 6: FN<6>(ARGS, ST); break;                    \
-    case 7: FN<7>(ARGS, ST); break;                    \
-    case 8: FN<8>(ARGS, ST); break;                    \
-    default: return hipErrorInvalidValue;              \
-  }
-
 hipError_t launch_add_layernorm_fwd(const LnFwdArgs& a, hipStream_t stream) {
-  if (a.d % 4 != 0 || a.M <= 0) return hipErrorInvalidValue;
-  LN_DISPATCH(launch_fwd_c, a, stream);
+  if (a.M <= 0 || !ln_dispatch(a.d, [&](auto shape) { launch_fwd(shape, a, stream); })) return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
 hipError_t launch_layernorm_bwd(const LnBwdArgs& a, hipStream_t stream) {
-  if (a.d % 4 != 0 || a.M <= 0 || a.ws == nullptr) return hipErrorInvalidValue;
-  LN_DISPATCH(launch_bwd_c, a, stream);
+  if (a.M <= 0 || a.ws == nullptr || !ln_dispatch(a.d, [&](auto shape) { launch_bwd(shape, a, stream); }))
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
-namespace {
-template <int MAXC>
-void grid_c(const LnBwdArgs& a, int& out) { out = bwd_grid_c<MAXC>(a); }
-}  // namespace
-
 int layernorm_bwd_grid(const LnBwdArgs& a) {
-  if (a.d % 4 != 0 || a.M <= 0) return 0;
   int grid = 0;
-  switch ((a.d / 4 + 63) / 64) {
-    case 1: grid_c<1>(a, grid); break;
-    case 2: grid_c<2>(a, grid); break;
-    case 3: grid_c<3>(a, grid); break;
-    case 4: grid_c<4>(a, grid); break;
-    case 5: grid_c<5>(a, grid); break;
-    case 6: grid_c<6>(a, grid); break;
-    case 7: grid_c<7>(a, grid); break;
-    case 8: grid_c<8>(a, grid); break;
-    default: return 0;
-  }
+  if (a.M > 0) ln_dispatch(a.d, [&](auto shape) { grid = bwd_grid(shape, a); });
   return grid;
 }
 
 long layernorm_bwd_ws_floats(const LnBwdArgs& a) {
-  if (a.d % 4 != 0 || a.M <= 0) return 0;
-  int grid = 0;
-  switch ((a.d / 4 + 63) / 64) {
-    case 1: grid_c<1>(a, grid); break;
-    case 2: grid_c<2>(a, grid); break;
-    case 3: grid_c<3>(a, grid); break;
-    case 4: grid_c<4>(a, grid); break;
-    case 5: grid_c<5>(a, grid); break;
-    case 6: grid_c<6>(a, grid); break;
-    case 7: grid_c<7>(a, grid); break;
-    case 8: grid_c<8>(a, grid); break;
-    default: return 0;
-  }
+  const int grid = layernorm_bwd_grid(a);
   const int nacc = a.dproj != nullptr ? 3 : 2;
   return (long)nacc * grid * a.d + (long)nacc * colsum_scratch_floats(grid, a.d);
 }

@@ -30,7 +30,11 @@ from llmtrain.config.schemas import RunConfig
 from llmtrain.models.base import LazyFloat, ModelAdapter, validate_lm_batch
 from llmtrain.registry.models import register_model
 
-__all__ = ["GPT", "CausalSelfAttention", "GPTAdapter", "TransformerBlock"]
+__all__ = ["FUSED_MAX_D_MODEL", "GPT", "CausalSelfAttention", "GPTAdapter", "TransformerBlock"]
+
+# widest residual stream the fused engine's LayerNorm kernels take on the GPU (csrc/kernels.h
+# kLnMaxD): one wave per row up to 2048 columns, one workgroup per row above
+FUSED_MAX_D_MODEL = 8192
 
 
 class CausalSelfAttention(nn.Module):
@@ -171,7 +175,8 @@ class GPT(nn.Module):
         specialisation — GPT-2 124M and XL; the reference presets' 32 and 48 run zero-filled in
         the same tiles) or exactly 128 (two 64-wide halves; a 4-wave one-wave-per-
         SIMD backward) and key-padding masks; LayerNorm widths need d % 4 == 0,
-        d <= 2048.  Other shapes train on the module path.  On CPU the engine runs the reference
+        d <= ``FUSED_MAX_D_MODEL`` (8192: one wave per row up to 2048 columns, one workgroup per
+        row above).  Other shapes train on the module path.  On CPU the engine runs the reference
         ops, which take any shape.  Dropout is supported everywhere (counter-based masks fused into
         the embedding, add+LayerNorm and flash-attention kernels)."""
         if device_type != "cuda":
@@ -182,7 +187,7 @@ class GPT(nn.Module):
         return (
             ((hd % 8 == 0 and 8 <= hd <= 64) or hd == 128)
             and self.d_model % 4 == 0
-            and self.d_model <= 2048
+            and self.d_model <= FUSED_MAX_D_MODEL
             and self.d_ff % 8 == 0
         )
 

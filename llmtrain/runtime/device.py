@@ -90,15 +90,18 @@ def settle_fused_path(policy: RuntimePolicy, cfg: RunConfig, supported: bool) ->
     an uncovered shape is an error unless the config opts in with
     ``model.extra.allow_module_fallback: true`` (or asks for the module path with
     ``model.extra.fused: false``).  On CPU the module path is the reference numerics and is taken
-    silently.
+    silently.  The width bound in the error text is ``llmtrain.models.gpt.FUSED_MAX_D_MODEL``.
     """
+    from llmtrain.models.gpt import FUSED_MAX_D_MODEL  # models import this module
+
     if not policy.use_fused or supported:
         return policy
     if policy.device.type == "cuda" and not cfg.model.extra.get("allow_module_fallback", False):
         raise ValueError(
             f"the fused MI355X engine does not cover this model shape (d_model={cfg.model.d_model}, "
             f"n_heads={cfg.model.n_heads}, d_ff={cfg.model.d_ff}: head dims must be multiples of 8 up to 64, "
-            "or 128; d_model % 4 == 0 and <= 2048; d_ff % 8 == 0); set model.extra.allow_module_fallback: true "
+            f"or 128; d_model % 4 == 0 and <= {FUSED_MAX_D_MODEL}; d_ff % 8 == 0); set "
+            "model.extra.allow_module_fallback: true "
             "to train on the plain PyTorch module path instead, or model.extra.fused: false"
         )
     return RuntimePolicy(device=policy.device, compute_dtype=policy.compute_dtype, use_fused=False)
