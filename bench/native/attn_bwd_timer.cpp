@@ -30,9 +30,9 @@ void attn_bwd_probe_set(unsigned long long* buf);
   } while (0)
 
 int main(int argc, char** argv) {
-  // argv: B [label] [head_dim: 64 or 128; H keeps d_model = 768]
+  // argv: B [label] [head_dim: a multiple of 8 up to 128] [H; default keeps d_model = 768]
   const int D = argc > 3 ? std::atoi(argv[3]) : 64;
-  const int B = argc > 1 ? std::atoi(argv[1]) : 32, T = 1024, H = 768 / D;
+  const int B = argc > 1 ? std::atoi(argv[1]) : 32, T = 1024, H = argc > 4 ? std::atoi(argv[4]) : 768 / D;
   llmt::AttnDims dims;
   dims.B = B;
   dims.T = T;

@@ -1,4 +1,5 @@
-// Causal flash-attention backward, head_dim <= 64, for gfx950 (MI355X).
+// Causal flash-attention backward, head_dim a multiple of 8 in 8..128, for gfx950 (MI355X): the 8-wave
+// kernel described here for hd <= 64, the 4-wave attn_bwd128_kernel further down for 72..128.
 //
 // Replaces the autograd backward of reference models/gpt.py:56-69 (softmax + two batched
 // matmuls over materialised [B, H, T, T] tensors).  P is recomputed from Q, K and the forward's
@@ -34,7 +35,8 @@
 //    of LDS-active cycles at B=32 (the forward: 0).  The Q/dO row and transposed reads are
 //    conflict free by construction; the remainder is not attributed per access site (candidates:
 //    the 2-byte K^T image stores of the prologue and the 8-byte dS^T image stores);
-//  * SMALLHD (head dims < 64, multiples of 8) zero-fills the missing dims at load time; KMASK
+//  * SMALLHD (head dims < 64, multiples of 8; in the 4-wave kernel 72..120 on its 128-wide tiles)
+//    zero-fills the missing dims at load time; KMASK
 //    (key padding) zeroes P of this lane's key when it is padded — one per-lane flag, because the
 //    key sits on the MFMA lane here (rows the forward marked dead have lse = +inf, so P = 0).
 
@@ -81,7 +83,8 @@ constexpr int kQTile = 64;  // query rows per sweep step (two 32-row MFMA tiles)
 // workgroup stores its hd partial sums to vparts[b * gridDim.x + blockIdx.x][h * hd + d] (no
 // atomics: 512+ workgroups per head would serialise on the same 64 addresses);
 // launch_colsum_reduce sums them in a fixed order.
-// NH = 64-wide halves of the head dim (2: hd = 128): 8 * NH lanes per row, 32 / NH rows per sweep.
+// NH = 64-wide halves of the head dim (2: 64 < hd <= 128, SMALLHD below 128): 8 * NH lanes per row,
+// 32 / NH rows per sweep.
 constexpr int kDeltaRows = 256;
 template <bool SMALLHD, int NH = 1>
 __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_raw* __restrict__ dout,
@@ -176,6 +179,8 @@ __global__ __launch_bounds__(256) void attn_dq_reduce_kernel(const bf16_raw* __r
 #pragma unroll
     for (int it = 0; it < kSweeps; ++it) {
       const int t = min(t0 + kRps * it, T - 1);
+      // 64 < hd < 128: the 4-wave kernel leaves the plane columns at or past hd unwritten
+      if (SMALLHD && NH == 2 && 8 * c >= hd) continue;
       float x[8];
       unpack8(*reinterpret_cast<const ushort8_t*>(part + kb * plane + ((long)bh * T + t) * kW + 8 * c), x);
 #pragma unroll
@@ -657,21 +662,35 @@ __device__ __forceinline__ int kt128_off(int d, int key) {
   return d * kKv128 + ((((key >> 3) ^ (d & 15))) << 3) + (key & 7);
 }
 
-template <bool DROPOUT, bool KMASK>
+//
+// SMALLHD: head dims 72..120 (multiples of 8) on the same 128-wide tiles, as in the 8-wave kernel
+// below 64: runtime hd, strides and scale; K/V fragments and Q/dO chunks at or past hd come through
+// an out-of-record offset (zeros) — a real read would return the next head's data, or run past the
+// allocation for the last head of the last token; dK/dV, the dQ partial planes and the V-bias row
+// are stored only below hd.  The K^T image is built from the zero-filled fragments.
+// HDC: compile-time head dim of a named 72..120 shape (80, 96; 0 = runtime hd): the k-steps of
+// S = Q K^T and dP = dO V^T and the 32-wide blocks of dK^T / dV^T wholly past hd are neither held in
+// registers nor computed (hd 80: 5 of 8 k-steps, 3 of 4 blocks).
+template <bool DROPOUT, bool KMASK, bool SMALLHD, int HDC = 0>
 __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __restrict__ qkv,
                                                              const bf16_raw* __restrict__ dout,
                                                              const float* __restrict__ lse,
                                                              const float* __restrict__ delta,
                                                              bf16_raw* __restrict__ dqkv,
                                                              float* __restrict__ dq_part, float* __restrict__ vparts,
-                                                             int T, int H, int nkb, DropoutArgs dr,
+                                                             int T, int H, int nkb, DropoutArgs dr, int hd_arg,
+                                                             float scale_arg,
                                                              const uint8_t* __restrict__ key_valid) {
   resolve_dropout(dr);
-  constexpr int hd = 2 * kHD;
+  constexpr int kW = 2 * kHD;              // tile / dQ partial plane width
+  static_assert(HDC == 0 || (SMALLHD && HDC > kHD && HDC < kW && HDC % 8 == 0), "HDC: 72..120");
+  const int hd = HDC ? HDC : (SMALLHD ? hd_arg : kW);  // head dim in memory
+  constexpr int kKS = HDC ? (HDC + 15) / 16 : 8;       // 16-wide k-steps of S / dP that carry data
+  constexpr int kDT = HDC ? (HDC + 31) / 32 : 4;       // 32-wide blocks of dK^T / dV^T that carry data
   __shared__ __attribute__((aligned(16))) bf16_raw qd_lds[2][2][2][kQTile * kHD];  // [buf][Q|dO][half] 64 KB
   __shared__ __attribute__((aligned(16))) bf16_raw ds_lds[2][kKv128 * kQTile];     // [buf][key][q] 32 KB
   __shared__ __attribute__((aligned(16))) float rowc_lds[2][2 * kQTile];
-  __shared__ float bias_red[4][hd];
+  __shared__ float bias_red[4][kW];
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -699,16 +718,17 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
   const int kblk0 = kb * kKv128;
   const int kw0 = kblk0 + 32 * wave;
   const int key = kw0 + col;
-  constexpr float scale = 0.08838834764831845f;  // 1 / sqrt(128)
+  const float scale = SMALLHD ? scale_arg : 0.08838834764831845f;  // 1 / sqrt(hd)
   const float c = scale * 1.4426950408889634f;
   const bool kvalid = !KMASK || (key < T && key_valid[(long)b * T + key] != 0);
 
-  bf16x8 kf[8], vf[8];
+  bf16x8 kf[kKS], vf[kKS];
 #pragma unroll
-  for (int kk = 0; kk < 8; ++kk) {
+  for (int kk = 0; kk < kKS; ++kk) {
+    const bool live = !SMALLHD || 16 * kk + 8 * half < hd;
     const int off = (int)(key * row_stride + 16 * kk + 8 * half) * 2;
-    kf[kk] = __builtin_bit_cast(bf16x8, buf_load16(r_kv, off + hd * H * 2));
-    vf[kk] = __builtin_bit_cast(bf16x8, buf_load16(r_kv, off + 2 * hd * H * 2));
+    kf[kk] = __builtin_bit_cast(bf16x8, buf_load16(r_kv, live ? off + hd * H * 2 : kOobOff));
+    vf[kk] = __builtin_bit_cast(bf16x8, buf_load16(r_kv, live ? off + 2 * hd * H * 2 : kOobOff));
   }
   // dQ B operand (16x16x32, k = key, n = d): lane l holds K[32 ks + 8 (l >> 4) + 0..7][32 w + 16 dn + (l & 15)],
   // read once through a K^T image [128 d][128 keys] laid over both dS buffers
@@ -716,8 +736,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
   {
     bf16_raw* kt_img = ds_lds[0];
 #pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-      const ushort8_t kv = __builtin_bit_cast(ushort8_t, kf[kk]);
+    for (int kk = 0; kk < 8; ++kk) {  // all 128 rows of the image: zeros past the fragments held
+      const ushort8_t kv = kk < kKS ? __builtin_bit_cast(ushort8_t, kf[kk < kKS ? kk : 0]) : ushort8_t{0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
       for (int e = 0; e < 8; ++e) kt_img[kt128_off(16 * kk + 8 * half + e, 32 * wave + col)] = kv[e];
     }
@@ -739,8 +759,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
       const int cidx = threadIdx.x + 256 * (i & 3);
       const int r = cidx >> 4, ch = cidx & 15;
       const int qrow = q0 + r;
-      stg[i] = i < 4 ? buf_load16(r_q, (int)(qrow * row_stride + ch * 8) * 2)
-                     : buf_load16(r_do, (int)(qrow * out_stride + ch * 8) * 2);
+      const bool live = !SMALLHD || ch * 8 < hd;
+      stg[i] = i < 4 ? buf_load16(r_q, live ? (int)(qrow * row_stride + ch * 8) * 2 : kOobOff)
+                     : buf_load16(r_do, live ? (int)(qrow * out_stride + ch * 8) * 2 : kOobOff);
     }
     if (wave < 2) {  // wave 0: lse, wave 1: delta (wave-uniform descriptor choice)
       const int qq = q0 + (threadIdx.x & (kQTile - 1));
@@ -757,9 +778,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
     if (threadIdx.x < 2 * kQTile) rowc_lds[buf][threadIdx.x] = threadIdx.x < kQTile ? stc * 1.4426950408889634f : stc;
   };
 
-  f32x16 dk[4], dv[4];
+  f32x16 dk[kDT], dv[kDT];
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
+  for (int dt = 0; dt < kDT; ++dt) {
     dk[dt] = 0.f;
     dv[dt] = 0.f;
   }
@@ -774,7 +795,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
       if (active) {
         f32x16 p = 0.f, dp = 0.f;
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
+        for (int kk = 0; kk < kKS; ++kk) {
           const bf16x8 qa = lds_row_read(qd_lds[buf][0][kk >> 2], 32 * qs + col, 2 * (kk & 3) + half);
           const bf16x8 da = lds_row_read(qd_lds[buf][1][kk >> 2], 32 * qs + col, 2 * (kk & 3) + half);
           p = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[kk], p, 0, 0, 0);
@@ -818,7 +839,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
           const bf16x8 pb = pack_acc8(p, st);
           const bf16x8 sb = pack_acc8(ds, st);
 #pragma unroll
-          for (int dt = 0; dt < 4; ++dt) {
+          for (int dt = 0; dt < kDT; ++dt) {
             const int rb = 32 * qs + 16 * st + 4 * half;
             const bf16x8 doa = lds_tr_read_operand(qd_lds[buf][1][dt >> 1], rb, (dt & 1) * 32, lane);
             dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doa, pb, dv[dt], 0, 0, 0);
@@ -879,7 +900,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
         }
       }
       const int p = i & 1;
-      bf16_raw* plane = reinterpret_cast<bf16_raw*>(dq_part) + ((long)kb * gridDim.x + bh) * T * hd;
+      bf16_raw* plane = reinterpret_cast<bf16_raw*>(dq_part) + ((long)kb * gridDim.x + bh) * T * kW;
 #pragma unroll
       for (int qt = 0; qt < 4; ++qt) {
 #pragma unroll
@@ -891,7 +912,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
             const float sw = swap_pair(p ? acc[qt][dn][jj] : acc[qt][dn][2 + jj]);
             const float own = p ? acc[qt][dn][2 + jj] : acc[qt][dn][jj];
             const uint32_t w = (uint32_t)f2bf((p ? sw : own) * scale) | ((uint32_t)f2bf((p ? own : sw) * scale) << 16);
-            if (qq < T) *reinterpret_cast<uint32_t*>(plane + (long)qq * hd + 32 * wave + 16 * dn + (i & ~1)) = w;
+            // (the planes stay kW wide; the reduce reads only the columns below hd)
+            const int dcol = 32 * wave + 16 * dn + (i & ~1);
+            if (qq < T && (!SMALLHD || dcol < hd)) *reinterpret_cast<uint32_t*>(plane + (long)qq * kW + dcol) = w;
           }
         }
       }
@@ -901,7 +924,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
   if (key < T) {
     bf16_raw* dst = dqkv + ((long)b * T + key) * row_stride + (long)h * hd;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
+    for (int dt = 0; dt < kDT; ++dt) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         ushort4_t kv, vv;
@@ -911,14 +934,16 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
           vv[i] = f2bf(dv[dt][4 * g + i]);
         }
         const int d = dt * 32 + 8 * g + 4 * half;
-        *reinterpret_cast<ushort4_t*>(dst + hd * H + d) = kv;
-        *reinterpret_cast<ushort4_t*>(dst + 2 * hd * H + d) = vv;
+        if (!SMALLHD || d < hd) {  // hd % 8 == 0 and d % 4 == 0: the 4-wide store ends at or below hd
+          *reinterpret_cast<ushort4_t*>(dst + hd * H + d) = kv;
+          *reinterpret_cast<ushort4_t*>(dst + 2 * hd * H + d) = vv;
+        }
       }
     }
   }
   if (!DROPOUT || vparts == nullptr) return;
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
+  for (int dt = 0; dt < kDT; ++dt) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       float vv = dv[dt][r];
@@ -939,13 +964,13 @@ __global__ __launch_bounds__(256, 1) void attn_bwd128_kernel(const bf16_raw* __r
 }  // namespace attn
 
 namespace {
-// key-block size of the backward: 256 (8-wave kernel) for hd <= 64, 128 for hd = 128
-int bwd_kvblk(int hd) { return hd == 2 * attn::kHD ? attn::kKv128 : attn::kKvBlk; }
-int bwd_plane_width(int hd) { return hd == 2 * attn::kHD ? 2 * attn::kHD : attn::kHD; }
+// key-block size of the backward: 256 (8-wave kernel) for hd <= 64, 128 (4-wave kernel) above
+int bwd_kvblk(int hd) { return hd > attn::kHD ? attn::kKv128 : attn::kKvBlk; }
+int bwd_plane_width(int hd) { return hd > attn::kHD ? 2 * attn::kHD : attn::kHD; }
 }  // namespace
 
 long attn_bwd_workspace_floats(int B, int T, int H, int hd) {
-  if (hd == 2 * attn::kHD) {  // bf16 partial planes, one per 128-key block
+  if (hd > attn::kHD) {  // bf16 partial planes (128 wide for every hd in 72..128), one per 128-key block
     const long nkb = (T + bwd_kvblk(hd) - 1) / bwd_kvblk(hd);
     return (nkb * B * H * (long)T * bwd_plane_width(hd) + 1) / 2;
   }
@@ -997,12 +1022,20 @@ static void launch_bwd_variant(dim3 grid, hipStream_t stream, const bf16_raw* qk
                        lse, delta, dqkv, dq_acc, vparts, qparts, d.T, d.H, nkb, dr, d.hd, d.scale, d.key_valid);
 }
 
+// the (dropout, key mask) instantiation of the 4-wave kernel for one head-dim form
+template <bool SMALLHD, int HDC>
+static auto bwd128_variant(bool drop, bool km) {
+  return drop ? (km ? attn::attn_bwd128_kernel<true, true, SMALLHD, HDC> : attn::attn_bwd128_kernel<true, false, SMALLHD, HDC>)
+              : (km ? attn::attn_bwd128_kernel<false, true, SMALLHD, HDC> : attn::attn_bwd128_kernel<false, false, SMALLHD, HDC>);
+}
+
 hipError_t launch_attn_bwd(const void* dout, const void* qkv, const void* out, const float* lse, void* dqkv,
                            float* delta, float* dq_part, float* dbias, float* bias_ws, const AttnDims& d,
                            DropoutArgs dropout, hipStream_t stream, bool delta_ready) {
   const int B = d.B, T = d.T, H = d.H, hd = d.hd;
   const bool hd128 = hd == 2 * attn::kHD;
-  if (B <= 0 || T <= 0 || H <= 0 || T > 65535 || hd <= 0 || (hd > attn::kHD && !hd128) || hd % 8 != 0)
+  const bool wide = hd > attn::kHD;  // 72..128: the 128-wide tiles and the 4-wave kernel
+  if (B <= 0 || T <= 0 || H <= 0 || T > 65535 || hd <= 0 || hd > 2 * attn::kHD || hd % 8 != 0)
     return hipErrorInvalidValue;
   if (dbias != nullptr && bias_ws == nullptr) return hipErrorInvalidValue;
   const long rows = (long)B * T * H;
@@ -1015,7 +1048,8 @@ hipError_t launch_attn_bwd(const void* dout, const void* qkv, const void* out, c
   const bool small = hd < attn::kHD;
   if (!delta_ready) {
     auto dk = hd128 ? attn::attn_delta_kernel<false, 2>
-                    : (small ? attn::attn_delta_kernel<true> : attn::attn_delta_kernel<false>);
+              : wide ? attn::attn_delta_kernel<true, 2>
+                     : (small ? attn::attn_delta_kernel<true> : attn::attn_delta_kernel<false>);
     hipLaunchKernelGGL(dk, dgrid, dim3(256), 0, stream, (const bf16_raw*)dout, (const bf16_raw*)out, delta,
                        v_from_delta ? vparts : nullptr, T, H, hd);
   }
@@ -1029,15 +1063,18 @@ hipError_t launch_attn_bwd(const void* dout, const void* qkv, const void* out, c
   // the main kernel forms the V-bias partials with dropout (per key block)
   float* vp = drop ? vparts : nullptr;
   int nq_rows = bp.nq;  // partial rows of the Q-bias column sums
-  if (hd128) {
-    auto k = drop ? (km ? attn::attn_bwd128_kernel<true, true> : attn::attn_bwd128_kernel<true, false>)
-                  : (km ? attn::attn_bwd128_kernel<false, true> : attn::attn_bwd128_kernel<false, false>);
+  if (wide) {
+    // 128: the constant-hd form; 80 and 96: compile-time k-step / block counts; else runtime hd
+    auto k = hd128     ? bwd128_variant<false, 0>(drop, km)
+             : hd == 80 ? bwd128_variant<true, 80>(drop, km)
+             : hd == 96 ? bwd128_variant<true, 96>(drop, km)
+                        : bwd128_variant<true, 0>(drop, km);
     hipLaunchKernelGGL(k, dim3(B * H, nkb), dim3(256), 0, stream, q, g, lse, delta, dq, dq_part, vp, T, H, nkb,
-                       dropout, d.key_valid);
+                       dropout, hd, d.scale, d.key_valid);
     // dQ: sum of the key blocks' bf16 partial planes (+ the Q-bias partial rows)
-    hipLaunchKernelGGL((attn::attn_dq_reduce_kernel<false, 2>), dim3(B * H, (T + attn::kDqRows - 1) / attn::kDqRows),
-                       dim3(256), 0, stream, (const bf16_raw*)dq_part, dq, qparts, T, H, hd, nkb,
-                       rows * (long)bwd_plane_width(hd), kvblk);
+    auto rk = hd128 ? attn::attn_dq_reduce_kernel<false, 2> : attn::attn_dq_reduce_kernel<true, 2>;
+    hipLaunchKernelGGL(rk, dim3(B * H, (T + attn::kDqRows - 1) / attn::kDqRows), dim3(256), 0, stream,
+                       (const bf16_raw*)dq_part, dq, qparts, T, H, hd, nkb, rows * (long)bwd_plane_width(hd), kvblk);
   } else {
   // one workgroup per (b, h) over its key blocks (fp32 dQ inside, no reduce pass) when B*H fills
   // the CUs evenly (>= 85 % of the slots of its last round) and there is no dropout (the dropout

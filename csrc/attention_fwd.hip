@@ -1,4 +1,5 @@
-// Causal flash-attention forward, head_dim <= 64, bf16 in / bf16 out, for gfx950 (MI355X).
+// Causal flash-attention forward, head_dim a multiple of 8 in 8..128, bf16 in / bf16 out, for gfx950
+// (MI355X).
 //
 // Replaces reference models/gpt.py:49-71 (qkv split, Q K^T / sqrt(hd), causal masked_fill,
 // softmax, P V), which materialises [B, H, T, T] fp32 scores; here nothing of size T^2 ever
@@ -31,7 +32,11 @@
 //    docs/round6.md section 18): the loop is bound by VALU issue (~130 VALU per 16 MFMA per
 //    wave-tile), and what pays is more resident waves, not intra-wave pipelining;
 //  * SMALLHD: head dims below 64 (multiples of 8: the reference presets' 32 and 48) run the same
-//    64-wide tiles with the missing dims zero-filled at load time and never stored;
+//    64-wide tiles with the missing dims zero-filled at load time and never stored; head dims
+//    72..120 (GPT-3 2.7B's 80, 760M's 96) run the hd = 128 form (NH = 2) the same way: runtime hd,
+//    strides and softmax scale, chunks at or past hd loaded through an out-of-record offset (a real
+//    read would return the NEXT head's data, or run past the allocation for the last head of the
+//    last token), output dims at or past hd never stored;
 //  * KMASK: key-padding mask (reference gpt.py:60-64) from one 64-bit word per 64-key tile (a
 //    scalar load: the tile's keys are wave-uniform); padded keys score -inf like future keys.  A
 //    row whose keys so far are ALL masked keeps m = -inf: its exponent offset is taken as 0 then
@@ -99,9 +104,12 @@ __device__ __forceinline__ void dma_kv(unsigned lds_k, unsigned lds_v, int v0, i
       : "memory", "scc");
 }
 
-// NH: 64-wide halves of the head dim (1: hd <= 64; 2: hd = 128, every [64][128] K/V tile kept as two
-// [64][64] LDS images so the swizzle and fragment readers stay the 64-wide ones)
-template <bool DROPOUT, bool KMASK, bool SMALLHD, int NH = 1>
+// NH: 64-wide halves of the head dim (1: hd <= 64; 2: 64 < hd <= 128, every [64][128] K/V tile kept
+// as two [64][64] LDS images so the swizzle and fragment readers stay the 64-wide ones; SMALLHD with
+// NH = 2 is 64 < hd < 128)
+// HDC: compile-time head dim of a named 72..120 shape (80, 96; 0 = runtime hd): the k-steps of
+// S^T = K Q^T and the 32-wide blocks of O that lie wholly past hd are not computed at all.
+template <bool DROPOUT, bool KMASK, bool SMALLHD, int NH = 1, int HDC = 0>
 __global__ __launch_bounds__(256, NH == 1 ? 4 : 2) void attn_fwd_kernel(const bf16_raw* __restrict__ qkv,
                                                           bf16_raw* __restrict__ out,
                                                           float* __restrict__ lse, int T, int H,
@@ -122,7 +130,10 @@ __global__ __launch_bounds__(256, NH == 1 ? 4 : 2) void attn_fwd_kernel(const bf
   chunked_dispatch(bh, qrank);
   const int qb = nqb - 1 - qrank;
   const int b = bh / H, h = bh - b * H;
-  const int hd = SMALLHD ? hd_arg : kHD * NH;  // head dim in memory; tiles stay 64 wide
+  static_assert(HDC == 0 || (SMALLHD && NH == 2 && HDC > kHD && HDC < 2 * kHD && HDC % 8 == 0), "HDC: 72..120");
+  const int hd = HDC ? HDC : (SMALLHD ? hd_arg : kHD * NH);  // head dim in memory; tiles stay 64 wide
+  constexpr int kKS = HDC ? (HDC + 15) / 16 : 4 * NH;  // 16-wide k-steps of S^T that carry data
+  constexpr int kDT = HDC ? (HDC + 31) / 32 : 2 * NH;  // 32-wide blocks of O that carry data
   const long row_stride = 3L * H * hd;   // elements between consecutive tokens in qkv
   const bf16_raw* base = qkv + (long)b * T * row_stride + (long)h * hd;
   // attention-probability dropout: plane seed per (b, h), element index q*T + key
@@ -133,9 +144,9 @@ __global__ __launch_bounds__(256, NH == 1 ? 4 : 2) void attn_fwd_kernel(const bf
   const int q_hi = min(q0w + 31, T - 1);     // last valid query row of the wave
 
   // Q fragments (B operand of S^T = K Q^T): lane holds Q[q][16kk + 8*half + 0..7]
-  bf16x8 qf[4 * NH];
+  bf16x8 qf[kKS];
 #pragma unroll
-  for (int kk = 0; kk < 4 * NH; ++kk) {
+  for (int kk = 0; kk < kKS; ++kk) {
     ushort8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
     if (q < T && (!SMALLHD || 16 * kk + 8 * half < hd))
       v = *reinterpret_cast<const ushort8_t*>(base + (long)q * row_stride + 16 * kk + 8 * half);
@@ -145,7 +156,7 @@ __global__ __launch_bounds__(256, NH == 1 ? 4 : 2) void attn_fwd_kernel(const bf
     // retire the Q loads here: the compiler counts only its own VMEM ops, so a first use of qf inside
     // the tile loop would get a counted wait there that also drains the in-flight K/V LDS-DMA
 #pragma unroll
-    for (int kk = 0; kk < 4 * NH; ++kk) asm volatile("" : "+v"(qf[kk]));
+    for (int kk = 0; kk < kKS; ++kk) asm volatile("" : "+v"(qf[kk]));
   }
 
   const int kv_end = min(T, qb * kQBlk + kQBlk);
@@ -184,9 +195,9 @@ __global__ __launch_bounds__(256, NH == 1 ? 4 : 2) void attn_fwd_kernel(const bf
     }
   };
 
-  f32x16 o[2 * NH];
+  f32x16 o[kDT];
 #pragma unroll
-  for (int dt = 0; dt < 2 * NH; ++dt) o[dt] = 0.f;
+  for (int dt = 0; dt < kDT; ++dt) o[dt] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
   const float c = (SMALLHD || NH != 1) ? c_arg : 0.125f * 1.4426950408889634f;  // softmax scale * log2(e)
   const int nkw = (T + kKBlk - 1) / kKBlk;  // key-mask words per sequence
@@ -233,7 +244,7 @@ __global__ __launch_bounds__(256, NH == 1 ? 4 : 2) void attn_fwd_kernel(const bf
       for (int kt = 0; kt < 2; ++kt) {
         s[kt] = 0.f;
 #pragma unroll
-        for (int kk = 0; kk < 4 * NH; ++kk) {
+        for (int kk = 0; kk < kKS; ++kk) {
           const bf16x8 a = lds_row_read(smem[cur][0][kk >> 2], kt * 32 + col, 2 * (kk & 3) + half);
           s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[kk], s[kt], 0, 0, 0);
         }
@@ -278,7 +289,7 @@ __global__ __launch_bounds__(256, NH == 1 ? 4 : 2) void attn_fwd_kernel(const bf
         const float alpha = (KMASK && m_new == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f((m_run - m_new) * c);
         l_run *= alpha;
 #pragma unroll
-        for (int dt = 0; dt < 2 * NH; ++dt) o[dt] *= alpha;
+        for (int dt = 0; dt < kDT; ++dt) o[dt] *= alpha;
         m_run = m_new;
       }
       // an all-masked row so far (KMASK only) has m = -inf: offset 0 gives P = 0, not NaN
@@ -319,7 +330,7 @@ __global__ __launch_bounds__(256, NH == 1 ? 4 : 2) void attn_fwd_kernel(const bf
         for (int st = 0; st < 2; ++st) {
           const bf16x8 pb = pack_acc8(s[kt], st);
 #pragma unroll
-          for (int dt = 0; dt < 2 * NH; ++dt) {
+          for (int dt = 0; dt < kDT; ++dt) {
             const bf16x8 va = lds_tr_read_operand(smem[cur][1][dt >> 1], kt * 32 + 16 * st + 4 * half, (dt & 1) * 32, lane);
             o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pb, o[dt], 0, 0, 0);
           }
@@ -350,7 +361,7 @@ __global__ __launch_bounds__(256, NH == 1 ? 4 : 2) void attn_fwd_kernel(const bf
     const float inv_l = dead ? 0.f : 1.f / l_run;
     bf16_raw* dst = out + ((long)b * T + q) * H * hd + (long)h * hd;
 #pragma unroll
-    for (int dt = 0; dt < 2 * NH; ++dt) {
+    for (int dt = 0; dt < kDT; ++dt) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         ushort4_t v;
@@ -374,17 +385,17 @@ void attn_probe_set(unsigned long long* buf) {
 }
 #endif
 
-template <bool DROPOUT, bool KMASK, bool SMALLHD, int NH = 1>
+template <bool DROPOUT, bool KMASK, bool SMALLHD, int NH = 1, int HDC = 0>
 static void launch_fwd_variant(dim3 grid, hipStream_t stream, const bf16_raw* qkv, bf16_raw* out, float* lse,
                                const AttnDims& d, int nqb, DropoutArgs dr) {
-  hipLaunchKernelGGL((attn::attn_fwd_kernel<DROPOUT, KMASK, SMALLHD, NH>), grid, dim3(256), 0, stream, qkv, out, lse,
+  hipLaunchKernelGGL((attn::attn_fwd_kernel<DROPOUT, KMASK, SMALLHD, NH, HDC>), grid, dim3(256), 0, stream, qkv, out, lse,
                      d.T, d.H, nqb, dr, d.hd, d.scale * 1.4426950408889634f, d.key_bits);
 }
 
 hipError_t launch_attn_fwd(const void* qkv, void* out, float* lse, const AttnDims& d, DropoutArgs dropout,
                            hipStream_t stream) {
   const bool hd128 = d.hd == 2 * attn::kHD;
-  if (d.B <= 0 || d.T <= 0 || d.H <= 0 || d.T > 65535 || d.hd <= 0 || (d.hd > attn::kHD && !hd128) || d.hd % 8 != 0)
+  if (d.B <= 0 || d.T <= 0 || d.H <= 0 || d.T > 65535 || d.hd <= 0 || d.hd > 2 * attn::kHD || d.hd % 8 != 0)
     return hipErrorInvalidValue;
   const int nqb = (d.T + attn::kQBlk - 1) / attn::kQBlk;
   dim3 grid(d.B * d.H, nqb);
@@ -399,6 +410,23 @@ hipError_t launch_attn_fwd(const void* qkv, void* out, float* lse, const AttnDim
       case 4: launch_fwd_variant<true, false, false, 2>(grid, stream, q, o, lse, d, nqb, dropout); break;
       default: launch_fwd_variant<true, true, false, 2>(grid, stream, q, o, lse, d, nqb, dropout); break;
     }
+    return hipGetLastError();
+  }
+  if (d.hd > attn::kHD) {  // 72..120: the 128-wide tiles (dims past hd zero-filled); 80 and 96 with compile-time counts
+#define LLMT_FWD_MID(DR, KM)                                                                                   \
+  do {                                                                                                         \
+    if (d.hd == 80) launch_fwd_variant<DR, KM, true, 2, 80>(grid, stream, q, o, lse, d, nqb, dropout);         \
+    else if (d.hd == 96)  /* dropout + key mask at 96 spills 20 B with the counts: runtime form */            \
+      launch_fwd_variant<DR, KM, true, 2, (DR && KM) ? 0 : 96>(grid, stream, q, o, lse, d, nqb, dropout);      \
+    else launch_fwd_variant<DR, KM, true, 2>(grid, stream, q, o, lse, d, nqb, dropout);                        \
+  } while (0)
+    switch (variant) {
+      case 0: LLMT_FWD_MID(false, false); break;
+      case 2: LLMT_FWD_MID(false, true); break;
+      case 4: LLMT_FWD_MID(true, false); break;
+      default: LLMT_FWD_MID(true, true); break;
+    }
+#undef LLMT_FWD_MID
     return hipGetLastError();
   }
   switch (variant) {

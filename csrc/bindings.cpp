@@ -378,15 +378,16 @@ void embedding_bwd(const Tensor& dx, const Tensor& ids, Tensor dwte, Tensor dwpe
 }
 
 // ---- attention -------------------------------------------------------------------------------
-// head dim from the packed qkv [B*T, 3*H*hd]: a multiple of 8 up to 64 (the kernels' tiles are 64
-// wide; smaller heads are zero-filled in LDS/registers) or exactly 128 (two 64-wide halves)
+// head dim from the packed qkv [B*T, 3*H*hd]: a multiple of 8 up to 128 (the kernels' tiles are 64
+// wide up to 64 and two 64-wide halves above; heads narrower than the tile are zero-filled in
+// LDS/registers)
 int64_t attn_head_dim(const Tensor& qkv, int64_t B, int64_t T, int64_t H) {
   check_gpu(qkv, "qkv");
   check_dtype(qkv, at::kBFloat16, "qkv");
   TORCH_CHECK(B > 0 && T > 0 && H > 0 && qkv.numel() % (B * T * 3 * H) == 0, "qkv must be [B*T, 3*H*hd]");
   const int64_t hd = qkv.numel() / (B * T * 3 * H);
-  TORCH_CHECK((hd % 8 == 0 && hd >= 8 && hd <= 64) || hd == 128,
-              "attention kernels need head_dim % 8 == 0 and 8 <= head_dim <= 64, or head_dim == 128, got ", hd);
+  TORCH_CHECK(hd % 8 == 0 && hd >= 8 && hd <= 128,
+              "attention kernels need head_dim % 8 == 0 and 8 <= head_dim <= 128, got ", hd);
   return hd;
 }
 

@@ -198,15 +198,17 @@ inline long gemm_fused_ws_floats(int M, int N) {
   return (long)nparts * N + colsum_scratch_floats(nparts, N);
 }
 
-// ---- causal flash attention (head_dim <= 64, multiple of 8) ------------------------------
+// ---- causal flash attention (head_dim a multiple of 8 in 8..128) -------------------------
 // Shape + options shared by the forward and backward launchers.  The kernels are specialised for
-// head_dim 64 (GPT-2 124M/XL); any other multiple of 8 up to 64 (the reference presets' 32 and
-// 48) runs the same kernels with the missing head dims zero-filled in LDS/registers.  The optional
+// head_dim 64 (GPT-2 124M/XL) and 128 (two 64-wide halves); any other multiple of 8 runs the next
+// wider form with the missing head dims zero-filled in LDS/registers and never stored: 8..56 (the
+// reference presets' 32 and 48) on the 64-wide tiles, 72..120 (GPT-3 2.7B's 80, 760M's 96) on the
+// 128-wide ones.  Any other head dim is hipErrorInvalidValue.  The optional
 // key-padding mask (reference models/gpt.py:60-64) excludes keys from the softmax; a query row
 // whose every causal key is masked gets O = 0 and lse = +inf (P = 0 in the backward).
 struct AttnDims {
   int B = 0, T = 0, H = 0;
-  int hd = 64;                         // head dim
+  int hd = 64;                         // head dim: 8, 16, ..., 128
   float scale = 0.125f;                // softmax scale, 1/sqrt(hd)
   const uint64_t* key_bits = nullptr;  // fwd mask: [B, ceil(T/64)] words, bit j of word w = key 64w+j valid
   const uint8_t* key_valid = nullptr;  // bwd mask: [B, T], nonzero = key valid

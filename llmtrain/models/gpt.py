@@ -173,8 +173,9 @@ class GPT(nn.Module):
         """Whether the fused engine covers this shape on ``device_type``.  On the GPU the
         flash-attention kernels take head dims that are multiples of 8 up to 64 (64 is the fast
         specialisation — GPT-2 124M and XL; the reference presets' 32 and 48 run zero-filled in
-        the same tiles) or exactly 128 (two 64-wide halves; a 4-wave one-wave-per-
-        SIMD backward) and key-padding masks; LayerNorm widths need d % 4 == 0,
+        the same tiles) or, above 64, up to 128 (two 64-wide halves; a 4-wave
+        one-wave-per-SIMD backward; 72..120 — GPT-3 2.7B's 80, 760M's 96 — zero-filled in the
+        128-wide tiles) and key-padding masks; LayerNorm widths need d % 4 == 0,
         d <= ``FUSED_MAX_D_MODEL`` (8192: one wave per row up to 2048 columns, one workgroup per
         row above).  Other shapes train on the module path.  On CPU the engine runs the reference
         ops, which take any shape.  Dropout is supported everywhere (counter-based masks fused into
@@ -185,7 +186,7 @@ class GPT(nn.Module):
             return False
         hd = self.d_model // self.n_heads
         return (
-            ((hd % 8 == 0 and 8 <= hd <= 64) or hd == 128)
+            (hd % 8 == 0 and 8 <= hd <= 128)
             and self.d_model % 4 == 0
             and self.d_model <= FUSED_MAX_D_MODEL
             and self.d_ff % 8 == 0

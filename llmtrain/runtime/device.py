@@ -99,8 +99,8 @@ def settle_fused_path(policy: RuntimePolicy, cfg: RunConfig, supported: bool) ->
     if policy.device.type == "cuda" and not cfg.model.extra.get("allow_module_fallback", False):
         raise ValueError(
             f"the fused MI355X engine does not cover this model shape (d_model={cfg.model.d_model}, "
-            f"n_heads={cfg.model.n_heads}, d_ff={cfg.model.d_ff}: head dims must be multiples of 8 up to 64, "
-            f"or 128; d_model % 4 == 0 and <= {FUSED_MAX_D_MODEL}; d_ff % 8 == 0); set "
+            f"n_heads={cfg.model.n_heads}, d_ff={cfg.model.d_ff}: head dims must be multiples of 8 up to 128"
+            f"; d_model % 4 == 0 and <= {FUSED_MAX_D_MODEL}; d_ff % 8 == 0); set "
             "model.extra.allow_module_fallback: true "
             "to train on the plain PyTorch module path instead, or model.extra.fused: false"
         )
